@@ -10,9 +10,12 @@ the CPU baseline and one or two numbers per secondary workload; the full record 
 CPU sample description) goes to bench_detail.json next to this file and to stderr BEFORE that line.
 
 What the record carries (all measured in this process, on this GPU):
-  * value / ms_per_step: the timed region is a hipGraph of back-to-back launches (a multiple of --steps), replayed until
-    it lasts >= --min-seconds (0.5 s): `steps` echoes the flag, `steps_timed` is what was really timed.  Inputs are
-    resident in HBM and ROTATE over enough distinct sets (> 2x the 256 MiB Infinity Cache) that every step streams from HBM.
+  * value / ms_per_step: the timed region is exactly --steps back-to-back launches issued from hipGraphs (`steps_timed` = `steps`);
+    ms_per_step = wall time of that region / steps.  Inputs are resident in HBM and ROTATE over enough distinct sets (> 2x the
+    256 MiB Infinity Cache) that every step streams from HBM.  The secondary legs below replay their graphs until --min-seconds.
+  * --dump-outputs DIR: after the timed region, C of its last step (what the caller of the headline path receives) goes to DIR/C.npy,
+    float32 (float64 for f64), shape (problems, m, n) in row-major order; above 64 MB a fixed, seeded sample of the problems.  The inputs
+    depend on the arguments only, so two builds of the project can be compared output for output.
   * roofline: algorithmic bytes (br*(m*k*sA + k*n*sB) + m*n*sC*(1+[beta=1]) per problem) / HIP-event time per launch.
     `traffic` = TCC-counter bytes per launch from the committed PMC pass of this same command (profiles/), null if none.
   * verified: after the timed region a strided sample of C is compared with the oracle (oracle/liboracle.so) on the same inputs.
@@ -63,7 +66,7 @@ L3_BYTES = 256 * 2 ** 20
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="launches in the headline's timed region (exactly)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=2, choices=[2, 5], help="BASELINE config: 2 = f32 32^3 batch 4096 (headline), 5 = bf16 64^3 fused, 2^20 problems sharded")
     ap.add_argument("--m", type=int, default=32, help="m = n = k")
@@ -73,7 +76,7 @@ def parse():
     ap.add_argument("--beta", type=int, default=0, choices=[0, 1])
     ap.add_argument("--fused", type=int, default=0, help="1: bf16 column-bias + ReLU epilogue")
     ap.add_argument("--sets", type=int, default=0, help="distinct input sets to rotate over (0: auto, > 2x L3)")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="minimum length of the timed region")
+    ap.add_argument("--min-seconds", type=float, default=0.5, help="minimum length of a secondary leg's timed region")
     ap.add_argument("--total", type=int, default=1 << 20, help="--config 5: problems over all ranks")
     ap.add_argument("--gather", action="store_true", help="--config 5: also time the gather of C to rank 0 (RCCL)")
     ap.add_argument("--no-sweep", action="store_true", help="headline only (profiling passes)")
@@ -85,6 +88,7 @@ def parse():
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE configs #3 / #4 / #5 legs")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the full record goes (the stdout line is the compact one)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write C of the last timed step to DIR/C.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--cpu-threads", type=int, default=-1, help="threads of the all-core CPU leg (-1: one per usable core, 0/1: skip)")
     return ap.parse_args()
 
@@ -386,6 +390,74 @@ def timed(work, steps, min_seconds, barrier=lambda: None, label=None, lanes=0):
                      "algorithmic_bytes_per_launch": int(work.alg_bytes_per_step), "flops_per_launch": work.flops_per_step, "dtype": work.dtype,
                      "us_per_launch_events": e0.elapsed_time(e1) * 1e3 / n})
     return t1 - t0, n, e0.elapsed_time(e1) * 1e3 / n
+
+
+def timed_steps(work, steps, barrier=lambda: None, label=None):
+    """Exactly `steps` launches, step i on input set i % nsets as in timed(): a graph of `chunk` launches (a multiple of the rotation, at most
+    ~2000) replayed steps // chunk times, then one graph of the remaining launches, which carries the rotation on.  Both graphs are replayed
+    once untimed first (upload).  Returns (wall seconds, launches timed, us per launch from HIP events recorded on the launch stream)."""
+    work.api.hip_set_streaming_hint(work.hint)
+    steps = max(1, steps)
+    chunk = work.nsets * max(1, min(steps, 2000) // work.nsets)
+    full, rest = divmod(steps, chunk)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    if EAGER:
+        barrier(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        for i in range(steps):
+            work.step(i)
+        e1.record()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        barrier()
+    else:
+        plan = [(capture(work, chunk), full)] if full else []
+        if rest:
+            plan.append((capture(work, rest), 1))
+        for g, _ in plan:
+            g.replay()
+        torch.cuda.synchronize()
+        barrier(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        for g, reps in plan:
+            for _ in range(reps):
+                g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        barrier()
+    # graphs: the launch counter saw every captured launch once at capture, the GPU executed each of them once in the upload replay, then the timed ones
+    executed = int(work.api.hip_launch_count(1)) + (0 if EAGER else steps)
+    work.api.hip_set_streaming_hint(0)
+    MANIFEST.append({"label": label or work.label(), "kernel": work.kernel(), "launches_executed": executed, "launches_timed": steps, "streaming_hint": work.hint,
+                     "kernels_per_launch": getattr(work, "kernels_per_launch", 1), "lanes": 0,
+                     "algorithmic_bytes_per_launch": int(work.alg_bytes_per_step), "flops_per_launch": work.flops_per_step, "dtype": work.dtype,
+                     "us_per_launch_events": e0.elapsed_time(e1) * 1e3 / steps})
+    return t1 - t0, steps, e0.elapsed_time(e1) * 1e3 / steps
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(work, steps, out_dir):
+    """--dump-outputs: C of the last timed step (input set (steps - 1) % nsets) as DIR/C.npy, one m x n matrix per problem in row-major order
+    (the library stores each column-major), 16-bit results widened to float32.  Above DUMP_BYTES: the problems of a fixed, seeded sample."""
+    m, batch = work.m, work.batch
+    c = work.C[(max(1, steps) - 1) % work.nsets][:batch * m * m].view(batch, m * m)
+    odt = torch.float64 if work.f64 else torch.float32
+    per_problem = m * m * (8 if work.f64 else 4)
+    if batch * per_problem > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(batch, DUMP_BYTES // per_problem, replace=False))
+        c = c[torch.from_numpy(keep).to(c.device)]
+    if work.dtype == "f16":
+        c = c.view(torch.float16)
+    elif work.bf16:
+        c = c.view(torch.bfloat16)
+    host = c.to(odt).cpu().numpy().reshape(-1, m, m).transpose(0, 2, 1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "C.npy"), np.ascontiguousarray(host))
 
 
 def entry(work, steps, min_seconds, verify=True):
@@ -881,8 +953,10 @@ def run_config5(args, api, dev, rank, world, dist, barrier):
     for i in range(max(1, min(args.warmup, 5))):
         work.step(i)
     torch.cuda.synchronize(); api.check()
-    elapsed, n, us = timed(work, args.steps, args.min_seconds, barrier)
+    elapsed, n, us = timed_steps(work, args.steps, barrier)
     api.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(work, args.steps, args.dump_outputs)
     ok, err, cnt = work.verify(0)
     gather_ms = None
     if args.gather and dist is not None:
@@ -1017,8 +1091,10 @@ def main():
         work.step(i)
     torch.cuda.synchronize()
     api.check()
-    elapsed, n_timed, kernel_us = timed(work, args.steps, args.min_seconds, barrier)
+    elapsed, n_timed, kernel_us = timed_steps(work, args.steps, barrier)
     api.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(work, args.steps, args.dump_outputs)
     headline_kernel, headline_hint = work.kernel(), work.hint
     verified, verr, vcnt = (work.verify(0) if args.beta == 0 else (None, 0.0, 0))
     if dist is not None:

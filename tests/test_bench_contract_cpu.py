@@ -169,3 +169,41 @@ def test_launcher_environment_wins():
     """under the driver's own launcher (WORLD_SIZE set) bench.py must NOT spawn again"""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"WORLD_SIZE" not in os.environ and args.gpus > 1' in src
+
+
+def test_dump_outputs_writes_the_last_steps_c(tmp_path):
+    """--dump-outputs: C of the input set the last timed step wrote, one row-major m x n matrix per problem, 16-bit results widened to float32;
+    above 64 MB a fixed sample of the problems (the same one every run)."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    m, batch, nsets = 4, 6, 3
+    cs = [torch.arange(batch * m * m, dtype=torch.float32) + 1000 * s for s in range(nsets)]
+    work = types.SimpleNamespace(m=m, batch=batch, nsets=nsets, C=cs, f64=False, bf16=False, dtype="f32")
+    bench.dump_outputs(work, 5, str(tmp_path / "f32"))            # steps 0..4: the last one on set 4 % 3 = 1
+    got = np.load(tmp_path / "f32" / "C.npy")
+    assert got.dtype == np.float32 and got.shape == (batch, m, m)
+    want = cs[1].numpy().reshape(batch, m, m).transpose(0, 2, 1)   # the library stores each C column-major
+    assert np.array_equal(got, want)
+    # bf16: widened exactly
+    vals = torch.tensor([1.5, -2.0, 0.25, 3.0] * (m * m // 4) * batch, dtype=torch.float32)
+    work = types.SimpleNamespace(m=m, batch=batch, nsets=1, C=[vals.to(torch.bfloat16).view(torch.int16)], f64=False, bf16=True, dtype="bf16")
+    bench.dump_outputs(work, 1, str(tmp_path / "bf16"))
+    got = np.load(tmp_path / "bf16" / "C.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, vals.numpy().reshape(batch, m, m).transpose(0, 2, 1))
+    # too large: a seeded sample of whole problems, identical from call to call
+    old = bench.DUMP_BYTES
+    try:
+        bench.DUMP_BYTES = 2 * m * m * 4
+        work = types.SimpleNamespace(m=m, batch=batch, nsets=1, C=[cs[0]], f64=False, bf16=False, dtype="f32")
+        bench.dump_outputs(work, 1, str(tmp_path / "a"))
+        bench.dump_outputs(work, 1, str(tmp_path / "b"))
+    finally:
+        bench.DUMP_BYTES = old
+    a, b = np.load(tmp_path / "a" / "C.npy"), np.load(tmp_path / "b" / "C.npy")
+    assert a.shape == (2, m, m) and np.array_equal(a, b)
+    full = cs[0].numpy().reshape(batch, m, m).transpose(0, 2, 1)
+    assert all(any(np.array_equal(p, q) for q in full) for p in a)

@@ -4,6 +4,7 @@ Gold = numpy restatement of the block algorithm the reference's drivers carry (s
 eltwise_unary_quantization_to_mxbf8.c:22-71): byte arithmetic, bit-exact.  It is pinned on CPU against the reference's own TPP
 (libxsmm_reference_elementwise through oracle/_ref) and the GPU kernel is compared with it through the C-ABI."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -159,19 +160,36 @@ def _inputs(m, n, ldi, seed, specials):
     return bits, _f32_of_bf16(bits)
 
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mx_quant_reference.npz")
+
+
+def _reference_quant(key, bits, shape, data, scales):
+    """The reference's QUANT TPP on `bits` into data / scales; returns its rc.  Without oracle/_ref (the reference's sources are not readable
+    here) its outputs stored in tests/golden/mx_quant_reference.npz (tests/golden/make_mx_quant_golden.py) stand in; with it, they are checked too."""
+    pyoracle.build()
+    if not pyoracle.have_reference():
+        g = np.load(GOLDEN)
+        data[:], scales[:] = g[key + "_data"], g[key + "_scales"]
+        return int(g[key + "_rc"])
+    p = capi.UnaryParam()
+    p.in_.primary, p.out.primary, p.out.secondary = bits.ctypes.data, data.ctypes.data, scales.ctypes.data
+    rc = pyoracle.reference().lib.xref_reference_meltw_unary(C.byref(p), UNARY.QUANT, shape, 0)
+    if os.path.exists(GOLDEN):
+        g = np.load(GOLDEN)
+        assert int(g[key + "_rc"]) == rc and np.array_equal(g[key + "_data"], data) and np.array_equal(g[key + "_scales"], scales), "stored vectors are stale"
+    return rc
+
+
 CASES = [(64, 9, 64, 64, True), (64, 9, 72, 96, True), (32, 5, 32, 32, False), (96, 7, 100, 128, False), (256, 33, 256, 256, True), (128, 16, 128, 160, False)]
 
 
 @pytest.mark.parametrize("m,n,ldi,ldo,fp4", CASES)
 def test_numpy_gold_matches_the_reference_tpp(m, n, ldi, ldo, fp4):
-    ref = pyoracle.reference()
     bits, x = _inputs(m, n, ldi, 7, specials=n >= 7)
     out_dt = DT.MXFP4X2 if fp4 else DT.MXBF8
     data = np.zeros(n * (ldo // 2 if fp4 else ldo), np.uint8)
     scales = np.zeros(n * (ldo // 32), np.uint8)
-    p = capi.UnaryParam()
-    p.in_.primary, p.out.primary, p.out.secondary = bits.ctypes.data, data.ctypes.data, scales.ctypes.data
-    rc = ref.lib.xref_reference_meltw_unary(C.byref(p), UNARY.QUANT, capi.UnaryShape(m, n, ldi, ldo, DT.BF16, out_dt, DT.BF16), 0)
+    rc = _reference_quant(f"mx_{m}_{n}_{ldi}_{ldo}_{int(fp4)}", bits, capi.UnaryShape(m, n, ldi, ldo, DT.BF16, out_dt, DT.BF16), data, scales)
     if rc != 0:
         pytest.skip("the reference declines this QUANT descriptor")
     gd, gs = mx_quant_gold(x, m, n, ldi, ldo, fp4)
@@ -222,12 +240,9 @@ NV_CASES = [(64, 9, 64, 64), (32, 5, 40, 48), (96, 12, 100, 128), (16, 3, 16, 16
 
 @pytest.mark.parametrize("m,n,ldi,ldo", NV_CASES)
 def test_nvfp4_gold_matches_the_reference_tpp(m, n, ldi, ldo):
-    ref = pyoracle.reference()
     bits, x = _inputs(m, n, ldi, 7, specials=n >= 7)
     data, scales = np.zeros(n * (ldo // 2), np.uint8), np.zeros(n * (ldo // 16), np.uint8)
-    p = capi.UnaryParam()
-    p.in_.primary, p.out.primary, p.out.secondary = bits.ctypes.data, data.ctypes.data, scales.ctypes.data
-    rc = ref.lib.xref_reference_meltw_unary(C.byref(p), UNARY.QUANT, capi.UnaryShape(m, n, ldi, ldo, DT.BF16, DT.NVFP4X2, DT.BF16), 0)
+    rc = _reference_quant(f"nv_{m}_{n}_{ldi}_{ldo}", bits, capi.UnaryShape(m, n, ldi, ldo, DT.BF16, DT.NVFP4X2, DT.BF16), data, scales)
     if rc != 0:
         pytest.skip("the reference declines this QUANT descriptor")
     gd, gs = nvfp4_gold(x, m, n, ldi, ldo)
