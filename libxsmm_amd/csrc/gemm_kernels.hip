@@ -501,50 +501,6 @@ __device__ __forceinline__ void load_y_f32(float (&w)[16], GM const float* base,
   }
 }
 
-// Coalesced variant for exact tiles (measured with tools/gemm_probe.hip: +15% at batch 4096, equal to a
-// plain copy kernel at large batches): a 32x32 f32 operand tile is fetched with four fully coalesced
-// 16-byte-per-lane loads (whole 128-byte rows), parked in a wave-private 4 KiB LDS image and read back in
-// MFMA fragment order.  No barrier: the image is written and read by the same wave.
-//   KCONTIG == false (free index contiguous): image [k][f] linear, fragment = 16 conflict-free ds_read_b32.
-//   KCONTIG == true  (k contiguous): image [f][8 chunks of 4 k], chunk index XOR-swizzled with (f>>1)&7 so that
-//   the per-column ds_read_b128 is conflict free; v_permlane32_swap then interleaves the two k halves.
-template <bool KCONTIG>
-__device__ __forceinline__ void tile_gload(f32x4 (&g)[4], GM const float* base, long long ld, int f0, int k0, int lane) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int t = lane + 64 * q, hi = t >> 3, lo = (t & 7) * 4;
-    GM const float* src = KCONTIG ? base + (long long)(f0 + hi) * ld + k0 + lo : base + (long long)(k0 + hi) * ld + f0 + lo;
-    g[q] = *(GM const f32x4*)src;
-  }
-}
-template <bool KCONTIG>
-__device__ __forceinline__ void tile_to_frag(float (&w)[16], const f32x4 (&g)[4], float* lds, int lane) {
-  const int li = lane & 31, h = lane >> 5;
-  if (!KCONTIG) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ((f32x4*)lds)[lane + 64 * q] = g[q];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) w[s] = lds[(2 * s + h) * 32 + li];
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int t = lane + 64 * q, f = t >> 3, c = (t & 7) ^ ((f >> 1) & 7);
-      ((f32x4*)lds)[f * 8 + c] = g[q];
-    }
-    float v[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 x = ((const f32x4*)lds)[li * 8 + ((4 * h + q) ^ ((li >> 1) & 7))];
-      v[4 * q + 0] = x[0]; v[4 * q + 1] = x[1]; v[4 * q + 2] = x[2]; v[4 * q + 3] = x[3];
-    }
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[2 * s]), __float_as_uint(v[2 * s + 1]), false, false);
-      w[s] = __uint_as_float(r[0]); w[s + 8] = __uint_as_float(r[1]);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // f32, 32x32 MFMA tiles, MT x NT tiles per wave
 // ------------------------------------------------------------------------------------------------
@@ -732,103 +688,7 @@ __global__ __launch_bounds__(256) void gemm_f32_stream_kernel(GemmArgs p) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// The same algorithm for the case the headline benchmark is: a 1-D batch of independent 32x32x(32 br kchunks) problems with 16-byte
-// aligned strided operands, beta = 0 and no fused epilogue.  A launch of 4096 such problems is ONE round of waves that lasts ~10 us, so the
-// time every wave spends before its first load is issued is on the critical path of the whole launch.  The general kernel above reads a
-// 280-byte argument block in several dependent scalar loads, divides by the tile count and walks the batch / batch-reduce / epilogue
-// options; this one takes an 88-byte block (one scalar load round trip), has no option left to test, and in its single-chunk form (br = 1,
-// k = 32) has no loop either.
-// NTL: non-temporal operand loads.  Measured (tools/headline_probe.hip, profiles/r02_copy_floor.csv): with operands coming from HBM they
-// save 0.5 us of a 9.9 us launch (they do not displace the Infinity Cache's contents), but operands that ARE resident in the 256 MiB
-// Infinity Cache -- the normal case for a 48 MiB batch produced by the previous kernel -- are then not kept there: 8.7 instead of 5.8 us.
-// The launcher therefore asks for them only when one launch moves more than the Infinity Cache holds (they cannot be resident then).
-// ------------------------------------------------------------------------------------------------
-struct LeanF32Args {
-  const char* a; const char* b; char* c;
-  long long bs_a, bs_b, bs_c, brs_a, brs_b;          // batch strides, batch-reduce strides (bytes)
-  unsigned int nbatch, nchunks, kchunks, lda, ldb, ldc;   // nchunks = br_count * kchunks
-};
-// 16-byte operand load through a wave-uniform buffer resource with gfx950 cache-policy bits (aux: 1 = sc0, 2 = nt, 16 = sc1)
-template <int AUX> __device__ __forceinline__ f32x4 ld16_pol(__amdgpu_buffer_rsrc_t r, unsigned int voffset) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voffset, 0, AUX));
-}
-// POL 0: operands loaded `sc0 sc1`, C leaves as whole 16-byte pieces through the wave's LDS image, non-temporal.  Measured on the headline
-//        footprint (tools/policy_probe.hip, profiles/r02_cache_policy.txt): against plain loads + dword nt stores 9.95 vs 10.88 us with the
-//        operands in HBM AND 6.25 vs 6.7 us with the operands resident in the Infinity Cache -- no trade-off, so it is the default.
-// POL 1: operands loaded `nt`, C as dword nt stores: 9.65 us from HBM but 8.4 us on resident operands (an nt read is not kept in the
-//        Infinity Cache): only for launches that move more than the Infinity Cache holds, whose operands cannot be resident anyway.
-// POL 2: plain loads, dword nt stores (C not 16-byte aligned).
-// POL 3 (round 4): POL 1's nt loads with POL 0's 16-byte stores through the LDS image -- tools/headline_probe: a copy of this footprint with nt loads and 16-byte nt
-//        stores takes 8.99 us where the POL 1 kernel takes 9.99 (dword stores: four times the store instructions).
-template <bool TA, bool TB, bool SINGLE, int POL>
-__global__ __launch_bounds__(256) void gemm_f32_stream_kernel_lean(LeanF32Args p) {
-  constexpr int AUX = POL == 0 ? 17 : ((POL == 1 || POL == 3) ? 2 : 0);
-  __shared__ __attribute__((aligned(16))) float lds_all[4][2048];
-  const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const unsigned int bidx = blockIdx.x * 4u + wave;
-  if (bidx >= p.nbatch) return;
-  const unsigned int lane = threadIdx.x & 63u, li = lane & 31u, h = lane >> 5;
-  float* lds = lds_all[wave];
-  const unsigned int lda = p.lda, ldb = p.ldb, ldc = p.ldc;
-  gcptr ar = (gcptr)p.a + (long long)bidx * p.bs_a, br = (gcptr)p.b + (long long)bidx * p.bs_b;
-  const unsigned int offA = ((lane >> 3) * lda + (lane & 7u) * 4u) * 4u;
-  const unsigned int offB = ((lane >> 3) * ldb + (lane & 7u) * 4u) * 4u;
-  const unsigned int stepA = 32u * lda, stepB = 32u * ldb;          // bytes per 8 rows
-  f32x4 ga[4], gb[4];
-  {
-    const __amdgpu_buffer_rsrc_t ra = wave_rsrc(ar), rb = wave_rsrc(br);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) ga[x] = ld16_pol<AUX>(ra, x * stepA + offA);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) gb[x] = ld16_pol<AUX>(rb, x * stepB + offB);
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  if (SINGLE) {
-    float af[16], bf[16];
-    tile_to_frag<TA>(af, ga, lds, (int)lane);
-    tile_to_frag<!TB>(bf, gb, lds + 1024, (int)lane);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[s], af[s], acc, 0, 0, 0);
-  } else {
-    const unsigned long long kstepA = TA ? 128ull : 128ull * lda, kstepB = TB ? 128ull * ldb : 128ull;
-    unsigned int kc = 0;
-    for (unsigned int t = 0; t < p.nchunks; ++t) {
-      float af[16], bf[16];
-      tile_to_frag<TA>(af, ga, lds, (int)lane);
-      tile_to_frag<!TB>(bf, gb, lds + 1024, (int)lane);
-      if (++kc == p.kchunks) { kc = 0; ar += p.brs_a; br += p.brs_b; }
-      if (t + 1 < p.nchunks) {        // chunk t+1 is in flight while the matrix core works on chunk t
-        const __amdgpu_buffer_rsrc_t ra = wave_rsrc(ar + kc * kstepA), rb = wave_rsrc(br + kc * kstepB);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) ga[x] = ld16_pol<AUX>(ra, x * stepA + offA);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) gb[x] = ld16_pol<AUX>(rb, x * stepB + offB);
-      }
-#pragma unroll
-      for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[s], af[s], acc, 0, 0, 0);
-    }
-  }
-  gptr ctile = (gptr)p.c + (long long)bidx * p.bs_c;
-  if (POL == 0 || POL == 3) {
-    // C tile -> column-major LDS image (lanes along i: conflict free) -> whole 128-byte columns, 16 bytes per lane
-#pragma unroll
-    for (int r2 = 0; r2 < 16; ++r2) lds[li + (unsigned int)jl_of(r2, (int)h) * 32u] = acc[r2];
-    const __amdgpu_buffer_rsrc_t rc = wave_rsrc((gcptr)ctile);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      const unsigned int L = lane + 64u * x;
-      __builtin_amdgcn_raw_buffer_store_b128(((const u32x4*)lds)[L], rc, (int)(((L >> 3) * ldc + (L & 7u) * 4u) * 4u), 0, 2);
-    }
-  } else {
-    const unsigned int offC = (4u * h * ldc + li) * 4u;
-#pragma unroll
-    for (int r2 = 0; r2 < 16; ++r2)
-      st_stream((GM float*)(ctile + (unsigned long long)(((r2 & 3) + 8 * (r2 >> 2)) * ldc) * 4ull + offC), acc[r2]);
-  }
-}
+// (the lean form of this kernel for 1-D batches of whole 32 x 32 problems, gemm_f32_stream_kernel_lean: gemm_lean_kernels.hip)
 
 // ------------------------------------------------------------------------------------------------
 // ONE long STRIDE batch-reduce chain (SURVEY 8(d) config #2 variant B: a single BRGEMM with br = 4096): the chain is cut into slices, a workgroup
@@ -4720,31 +4580,15 @@ int launch_gemm(const GemmArgs& a_in, void* stream, const char** kernel_name) {
         else hipLaunchKernelGGL((gemm_f32_dma_kernel<1, 1, true, true>), grid, dim3(256), 0, st, a);
       }
       else if (pl.exact && operands_aligned16(a, 4) && f32_lean_ok(a)) {
-        const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B;
-        LeanF32Args la;
-        la.a = a.a; la.b = a.b; la.c = a.c; la.bs_a = a.bs_a; la.bs_b = a.bs_b; la.bs_c = a.bs_c;
-        la.brs_a = a.br_mode == 3 ? a.br_stride_a : 0; la.brs_b = a.br_mode == 3 ? a.br_stride_b : 0;
-        la.nbatch = a.nbatch; la.kchunks = (unsigned int)a.k >> 5; la.nchunks = (unsigned int)a.br_count * la.kchunks;
-        la.lda = (unsigned int)a.lda; la.ldb = (unsigned int)a.ldb; la.ldc = (unsigned int)a.ldc;
         if (kernel_name) *kernel_name = "gemm_f32_stream_kernel_lean";
         // cache policy (see the kernel).  Streaming hint of the calling thread (libxsmm_hip_set_streaming_hint): 2 = operands are read once
         // from HBM -> nt loads; 1 = operands are re-read / cache resident -> never nt; 0 (default) = decide by size: a launch that moves
-        // more than the Infinity Cache holds cannot have resident operands.  LIBXSMM_HIP_F32_POLICY=0|1|2 forces a kernel variant.
-        constexpr int pol_env = -1;
-        const unsigned long long footprint = (unsigned long long)a.nbatch * (a.br_count * (unsigned long long)(a.k) * 256ull + 4096ull);
+        // more than the Infinity Cache holds cannot have resident operands.
         const bool c16 = ((((unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c | (unsigned long long)((long long)a.ldc * 4)) & 15ull) == 0ull);
         int pol = stream_nt(a, 4, 4) ? 1 : 0;
-        (void)footprint;
         if (pol == 1 && c16) pol = 3;                        // nt loads AND whole 16-byte stores
-        if (pol_env >= 0 && pol_env <= 3) pol = pol_env;
         if ((pol == 0 || pol == 3) && !c16) pol = pol == 0 ? 2 : 1;
-#define LAUNCH_LEAN__(TA_, TB_, S_, P_) hipLaunchKernelGGL((gemm_f32_stream_kernel_lean<TA_, TB_, S_, P_>), grid, dim3(256), 0, st, la)
-#define LAUNCH_LEAN_S_(TA_, TB_, S_) do { if (pol == 0) LAUNCH_LEAN__(TA_, TB_, S_, 0); else if (pol == 1) LAUNCH_LEAN__(TA_, TB_, S_, 1); else if (pol == 3) LAUNCH_LEAN__(TA_, TB_, S_, 3); else LAUNCH_LEAN__(TA_, TB_, S_, 2); } while (0)
-#define LAUNCH_LEAN_(TA_, TB_) do { if (la.nchunks == 1) LAUNCH_LEAN_S_(TA_, TB_, true); else LAUNCH_LEAN_S_(TA_, TB_, false); } while (0)
-        if (!ta && !tb) LAUNCH_LEAN_(false, false); else if (ta && !tb) LAUNCH_LEAN_(true, false); else if (!ta && tb) LAUNCH_LEAN_(false, true); else LAUNCH_LEAN_(true, true);
-#undef LAUNCH_LEAN_S_
-#undef LAUNCH_LEAN__
-#undef LAUNCH_LEAN_
+        return launch_gemm_f32_lean(a, pol, stream);
       }
       else if (pl.exact && operands_aligned16(a, 4) && a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22)) {
         const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B;

@@ -244,6 +244,7 @@ void set_error(int code, const char* fmt, ...);
 int launch_gemm(const GemmArgs& args, void* stream, const char** kernel_name);
 int launch_gemm_f64(const GemmArgs& args, void* stream, const char** kernel_name);     // gemm_f64_kernels.hip: v_mfma_f64_16x16x4_f64
 const char* gemm_f64_kernel_name(const libxsmm_gemm_descriptor& d);
+int launch_gemm_f32_lean(const GemmArgs& args, int pol, void* stream);     // gemm_lean_kernels.hip: f32 32^3 1-D batches, pol = cache policy (launch_gemm)
 int launch_gemm_f32_wg64_sharedb(const GemmArgs& args, bool nt, void* stream, const char** kernel_name, int* taken);   // gemm_sharedb_kernels.hip: 64^3 f32, B shared by the batch
 int launch_gemm_p16w(const GemmArgs& args, bool nt, void* stream, const char** kernel_name, int* taken);
 int launch_gemm_wgp16(const GemmArgs& args, void* stream, const char** kernel_name, int* taken);
