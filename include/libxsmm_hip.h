@@ -136,6 +136,21 @@ LIBXSMM_API void libxsmm_hip_meltw_binary_batch_strided(libxsmm_meltwfunction_bi
   size_t count, long long stride_in0, long long stride_in1, long long stride_out);
 LIBXSMM_API void libxsmm_hip_meltw_ternary_batch_strided(libxsmm_meltwfunction_ternary kernel, const libxsmm_meltw_ternary_param* param,
   size_t count, long long stride_in0, long long stride_in1, long long stride_in2, long long stride_out);
+/**
+ * Strided batch of a matrix equation: element i (0 <= i < count) is the call kernel(&q) where q = *param except
+ *   q.inputs[k].primary   = (char*)param->inputs[k].primary   + i * stride_inputs[k]    (0 <= k < ninputs; 0 = shared: gamma, beta, eps, ...)
+ *   q.output.primary      = (char*)param->output.primary      + i * stride_output
+ *   q.output.secondary    = (char*)param->output.secondary    + i * stride_output_aux   (ReLU-bitmask / SCATTER-index head; unused otherwise)
+ *   q.ops_args[k].primary = (char*)param->ops_args[k].primary + i * stride_ops_args[k]  (0 <= k < nops_args; DUMP destinations)
+ * Everything else is shared by all elements: GATHER index lists (inputs[k].secondary), BRGEMM block counts (ops_args[k].tertiary) and scalar op
+ * arguments such as LEAKY_RELU's alpha.  Elements run concurrently, so a buffer that the caller's loop re-uses (the DUMP scratch of a softmax)
+ * needs a stride here.  Elements whose outputs overlap are undefined, as in the GEMM batches.  stride_ops_args may be NULL (all zero).
+ * Follows the thread's launch mode: blocking (1 x 1 inputs / a 1 x 1 output may be host memory), stream-ordered, or coalescing (the queue is
+ * flushed first).  Error -3: not an equation handle, or a non-zero stride on something shared; -2: ninputs below the equation's input positions.
+ */
+LIBXSMM_API void libxsmm_hip_meqn_batch_strided(libxsmm_meqn_function kernel, const libxsmm_meqn_param* param, size_t count,
+  int ninputs, const long long* stride_inputs, long long stride_output, long long stride_output_aux,
+  int nops_args, const long long* stride_ops_args);
 
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns

@@ -282,6 +282,8 @@ class Api:
             self.hip_meltw_unary_batch_strided = f("hip_meltw_unary_batch_strided", None, [vp, C.POINTER(UnaryParam), C.c_size_t, ll, ll, ll])
             self.hip_meltw_binary_batch_strided = f("hip_meltw_binary_batch_strided", None, [vp, C.POINTER(BinaryParam), C.c_size_t, ll, ll, ll])
             self.hip_meltw_ternary_batch_strided = f("hip_meltw_ternary_batch_strided", None, [vp, C.POINTER(TernaryParam), C.c_size_t, ll, ll, ll, ll])
+            pll = C.POINTER(ll)
+            self.hip_meqn_batch_strided = f("hip_meqn_batch_strided", None, [vp, C.POINTER(MeqnParam), C.c_size_t, C.c_int, pll, ll, ll, C.c_int, pll])
             pu = C.POINTER(C.POINTER(C.c_uint))
             self.hip_mtx_read = f("hip_mtx_read", C.c_int, [C.c_char_p, C.c_int, C.c_int, pu, pu, C.POINTER(vp), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)])
             self.hip_bcsc_from_dense = f("hip_bcsc_from_dense", C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, pu, pu, C.POINTER(vp), C.POINTER(C.c_uint)])

@@ -165,6 +165,7 @@ int jit_spmm_launch_slabs(JitKernel* k, const void* vals, const void* x, void* y
 void jit_release(JitKernel* k);
 JitKernel* jit_compile(const std::string& src, const std::string& fname, long long total_threads, int align_bytes, std::string* why);
 int jit_launch(JitKernel* k, void** args, void* stream);
+int jit_launch_grid(JitKernel* k, void** args, unsigned int grid_x, unsigned int grid_y, void* stream);     // explicit grid of 256-thread workgroups
 bool jit_on_current_device(const JitKernel* k);
 int rt_jit_mode();
 bool rt_dryrun();            // LIBXSMM_HIP_DRYRUN=1 and no device: dispatch / code generation work, nothing can be launched
@@ -206,6 +207,10 @@ struct KernelCtx {
 // ---- matrix equations (meqn.cpp) and the runtime services they use (runtime.cpp) ------------------------
 struct EqnPlan;
 void run_meqn(EqnPlan* plan, const void* param);
+// libxsmm_hip_meqn_batch_strided: `count` elements, byte strides per input position / output / output.secondary / op argument (NULL: all zero)
+struct MeqnBatch { size_t count; int ninputs; const long long* s_in; long long s_out, s_aux; int nops; const long long* s_ops; };
+bool meqn_batch_prepare(EqnPlan* plan, const MeqnBatch& b);                  // validation + the batched kernel (no device needed); false: error set
+const char* run_meqn_batch(EqnPlan* plan, const void* param, const MeqnBatch& b);     // returns the name of the kernel that ran (nullptr: nothing ran)
 void free_meqn_plan(EqnPlan* plan);
 void free_meqn_equations();                      // libxsmm_finalize: drop every equation object
 const char* meqn_plan_name(const EqnPlan* plan);

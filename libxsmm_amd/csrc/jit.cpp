@@ -314,6 +314,9 @@ int jit_launch(JitKernel* k, void** args, void* stream) {
   const unsigned int grid = (unsigned int)((k->total_threads + 255) / 256);
   return (int)hipModuleLaunchKernel(k->fn, grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
 }
+int jit_launch_grid(JitKernel* k, void** args, unsigned int grid_x, unsigned int grid_y, void* stream) {
+  return (int)hipModuleLaunchKernel(k->fn, grid_x, grid_y, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
+}
 bool jit_on_current_device(const JitKernel* k) {
   int dev = -1;
   return k && hipGetDevice(&dev) == hipSuccess && dev == k->device;

@@ -52,10 +52,15 @@ struct EqnPlan {
   std::vector<char> fused_scalar;   // ... and whether that argument is a 1 x 1 scalar (may live in host memory)
   std::vector<int> fused_alphas;    // op_arg positions of scalar op arguments, in kernel-argument order
   std::vector<int> fused_dumps;     // op_arg positions of DUMP destinations (device pointers), behind the alphas
+  std::vector<int> fused_types;     // datatype of each kernel argument
   std::vector<EqnStep> steps;
   std::vector<int> slot_of;         // per node: workspace slot (-1: none)
   size_t slot_bytes = 0; int nslots = 0;
   bool has_gemm = false;            // a MATMUL / BRGEMM step: room for the GEMM kernel's partial sums is reserved behind the slots
+  int ninputs = 0;                  // input positions the tree reads (largest in_pos + 1)
+  // libxsmm_hip_meqn_batch_strided: the batched form of `fused`, generated and compiled when the batched entry first meets the handle
+  int eqn_idx = -1; libxsmm_meqn_arg_shape out_shape{};
+  JitKernel* fused_b = nullptr; bool fused_b_tried = false; bool fused_b_phased = false; long long fused_b_total = 0;
 };
 
 namespace {
@@ -289,7 +294,10 @@ bool scalar_reduce(const Equation& e, int id, int M, int N, ScalarReduce& r) {
 // workgroup of 256 threads that walks the units once per reduction ("phase"), folds its partial results in LDS and carries the number in a
 // register into the phases that broadcast it -- the operand trees are re-evaluated from the (cache-resident) arguments, never written.  Unit t
 // belongs to thread t % 256 in every phase, so what a DUMP node wrote is read back (as an argument) by the thread that wrote it.
-bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eqn_idx, std::string& src, std::string& fname, EqnPlan& plan, long long& total) {
+// `batched`: the form libxsmm_hip_meqn_batch_strided launches (name + "_b").  The same walk emits the same per-element code; the kernel takes one byte
+// stride per input, for `out` and per DUMP destination plus the element count, and steps every pointer by element * stride at entry.  Phased form: one
+// workgroup per element (grid-stride over elements beyond the grid); element-wise form: the element is the second grid dimension (grid-stride as well).
+bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eqn_idx, bool batched, std::string& src, std::string& fname, EqnPlan& plan, long long& total) {
   const EqnNode& root = e.nodes[0];
   const bool scalar_root = root.m == 1 && root.n == 1;
   int M = root.m, N = root.n;                      // the extent of the element-wise part: the head's, or (a head that is one number) the operands'
@@ -482,29 +490,48 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
   if (arg_types.empty() || arg_types.size() > 24) return false;
   total = phased ? 256 : units;
   fname = std::string(phased ? "meqn_jit_r" : "meqn_jit_e") + std::to_string(eqn_idx) + "_" + std::to_string(M) + "x" + std::to_string(N) + "_o" + std::to_string((int)out.type);
+  if (batched) fname += "_b";
+  const std::string sfx = batched ? "_" : "";        // batched: the arguments are the element-0 pointers, the names the body uses are the stepped ones
   src = kFusedPrelude;
   src += "extern \"C\" __global__ __launch_bounds__(256) void " + fname + "(";
-  for (size_t k = 0; k < arg_types.size(); ++k) src += "const void* in" + std::to_string(k) + ", ";
-  src += "void* out";
+  for (size_t k = 0; k < arg_types.size(); ++k) src += "const void* in" + std::to_string(k) + sfx + ", ";
+  src += "void* out" + sfx;
   for (size_t k = 0; k < plan.fused_alphas.size(); ++k) src += ", float alpha" + std::to_string(k);
-  for (size_t k = 0; k < plan.fused_dumps.size(); ++k) src += ", void* dump" + std::to_string(k);
+  for (size_t k = 0; k < plan.fused_dumps.size(); ++k) src += ", void* dump" + std::to_string(k) + sfx;
+  std::string step;                                  // batched: the pointers of element `el`
+  if (batched) {
+    for (size_t k = 0; k < arg_types.size(); ++k) src += ", long long s_in" + std::to_string(k);
+    src += ", long long s_out";
+    for (size_t k = 0; k < plan.fused_dumps.size(); ++k) src += ", long long s_dump" + std::to_string(k);
+    src += ", long long count";
+    for (size_t k = 0; k < arg_types.size(); ++k) step += "  const void* in" + std::to_string(k) + " = (const char*)in" + std::to_string(k) + "_ + el * s_in" + std::to_string(k) + ";\n";
+    step += "  void* out = (char*)out_ + el * s_out;\n";
+    for (size_t k = 0; k < plan.fused_dumps.size(); ++k) step += "  void* dump" + std::to_string(k) + " = (char*)dump" + std::to_string(k) + "_ + el * s_dump" + std::to_string(k) + ";\n";
+  }
   src += ") {\n";
   const std::string store = std::string("  ") + (out.type == LIBXSMM_DATATYPE_F32 ? "st_f32((GM float*)" : "st_bf16((GM unsigned short*)") + "out + i + j * " + std::to_string((int)out.ld) + "LL, v0);\n";
   if (phased) {
-    src += "  __shared__ float part[256];\n" + lds_decl + phases;
-    if (scalar_root) src += out.type == LIBXSMM_DATATYPE_F32 ? "  if (threadIdx.x == 0) *(GM float*)out = " + head + ";\n}\n"
-                                                             : "  if (threadIdx.x == 0) *(GM unsigned short*)out = (unsigned short)(f2bf_pk(" + head + ", 0.0f) & 0xffffu);\n}\n";
-    else src += unit_loop + body + store + "  }\n}\n";
+    src += "  __shared__ float part[256];\n" + lds_decl;
+    // (batched: the barrier at the end of an element keeps the next element's phases from overwriting LDS the last phase still reads)
+    if (batched) src += "  for (long long el = blockIdx.x; el < count; el += gridDim.x) {\n" + step;
+    src += phases;
+    if (scalar_root) src += out.type == LIBXSMM_DATATYPE_F32 ? "  if (threadIdx.x == 0) *(GM float*)out = " + head + ";\n"
+                                                             : "  if (threadIdx.x == 0) *(GM unsigned short*)out = (unsigned short)(f2bf_pk(" + head + ", 0.0f) & 0xffffu);\n";
+    else src += unit_loop + body + store + "  }\n";
+    if (batched) src += "  __syncthreads();\n  }\n";
+    src += "}\n";
   } else {
     std::snprintf(buf, sizeof(buf), "  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;\n  if (t >= %lldLL) return;\n  const long long j = t / %d, i = (t - j * %d) * 8;\n", units, M / 8, M / 8);
     src += buf;
-    src += body + store + "}\n";
+    if (batched) src += "  for (long long el = blockIdx.y; el < count; el += gridDim.y) {\n" + step + body + store + "  }\n}\n";
+    else src += body + store + "}\n";
   }
   for (auto& a : arg_types) {
     plan.fused_inputs.push_back(a.first);
     char scalar = 0;
     for (const EqnNode& nd : e.nodes) if (nd.kind == EQ_ARG && nd.in_pos == a.first && nd.m == 1 && nd.n == 1) scalar = 1;
     plan.fused_scalar.push_back(scalar);
+    plan.fused_types.push_back(a.second);
   }
   return true;
 }
@@ -512,7 +539,7 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
 }  // namespace
 
 const char* meqn_plan_name(const EqnPlan* plan) { return (plan && plan->fused) ? jit_name(plan->fused) : "meqn_tpp_chain"; }
-void free_meqn_plan(EqnPlan* plan) { if (plan && plan->fused) jit_release(plan->fused); delete plan; }
+void free_meqn_plan(EqnPlan* plan) { if (plan && plan->fused) jit_release(plan->fused); if (plan && plan->fused_b) jit_release(plan->fused_b); delete plan; }
 // libxsmm_finalize: the equation objects (and their handle caches, whose handles the runtime has just released) go with the registry
 void free_meqn_equations() {
   std::lock_guard<std::mutex> guard(g_eqn_lock);
@@ -611,6 +638,191 @@ void run_meqn(EqnPlan* plan, const void* param) {
   rt_finish_launch(err, kname ? kname : "meqn");
 }
 
+// ---- strided batches (libxsmm_hip_meqn_batch_strided) ---------------------------------------------------------------------
+namespace {
+long long stride_of(const long long* s, int n, int k) { return (s && k >= 0 && k < n) ? s[k] : 0; }
+// 1 x 1 operands of every element that live in host memory (blocking mode): ONE block of (count - 1) * |stride| + bytes is staged, the
+// elements keep their offsets inside it
+char* stage_span(const void* p, long long stride, size_t count, size_t bytes, bool result) {
+  const long long lo = stride < 0 ? (long long)(count - 1) * stride : 0;
+  const size_t span = (size_t)((long long)(count - 1) * (stride < 0 ? -stride : stride)) + bytes;
+  char* base = result ? (char*)rt_small_host_output((char*)p + lo, span) : (char*)rt_small_host_input((const char*)p + lo, span);
+  return base ? base - lo : nullptr;
+}
+}  // namespace
+
+bool meqn_batch_prepare(EqnPlan* plan, const MeqnBatch& b) {
+  if (b.count >= (1ull << 31)) { set_error(-2, "matrix equation batch: count %zu is not below 2^31", b.count); return false; }
+  if (b.ninputs < plan->ninputs || (plan->ninputs > 0 && !b.s_in)) { set_error(-2, "matrix equation batch: %d input strides given, the equation reads %d input positions", b.ninputs, plan->ninputs); return false; }
+  if (b.nops < 0) { set_error(-2, "matrix equation batch: negative number of op-argument strides"); return false; }
+  // what every element shares must not be stepped: scalar op arguments (LEAKY_RELU's alpha), BRGEMM block counts, an UNZIP head's offset
+  for (const EqnStep& st : plan->steps) {
+    if (stride_of(b.s_ops, b.nops, st.alpha_from_op) != 0 || stride_of(b.s_ops, b.nops, st.br_from_op) != 0) {
+      set_error(-3, "matrix equation batch: op argument %d is shared by all elements (a scalar / block count): its stride must be 0", st.alpha_from_op >= 0 ? st.alpha_from_op : st.br_from_op); return false;
+    }
+    if (st.root_side == 2 && b.s_aux != 0) { set_error(-3, "matrix equation batch: the UNZIP head's offset (output.secondary) is shared: stride_output_aux must be 0"); return false; }
+  }
+  for (int pos : plan->fused_alphas) if (stride_of(b.s_ops, b.nops, pos) != 0) { set_error(-3, "matrix equation batch: op argument %d (alpha) is shared: its stride must be 0", pos); return false; }
+  std::lock_guard<std::mutex> guard(g_eqn_lock);
+  if (plan->fused && !plan->fused_b_tried) {
+    plan->fused_b_tried = true;
+    const Equation* e = get(plan->eqn_idx);
+    std::string src, fname; long long total = 0;
+    EqnPlan probe;
+    if (e && generate_fused(*e, plan->out_shape, plan->eqn_idx, true, src, fname, probe, total) && probe.fused_inputs == plan->fused_inputs &&
+        probe.fused_alphas == plan->fused_alphas && probe.fused_dumps == plan->fused_dumps) {
+      std::string why;
+      plan->fused_b = jit_compile(src, fname, total, 16, &why);
+      plan->fused_b_phased = fname.compare(0, 10, "meqn_jit_r") == 0; plan->fused_b_total = total;
+      if (!plan->fused_b && std::getenv("LIBXSMM_HIP_JIT_VERBOSE")) std::fprintf(stderr, "libxsmm_amd: generated batched equation kernel did not compile: %s\n%s\n", why.c_str(), src.c_str());
+    }
+  }
+  return true;
+}
+
+const char* run_meqn_batch(EqnPlan* plan, const void* param, const MeqnBatch& b) {
+  const libxsmm_meqn_param* p = (const libxsmm_meqn_param*)param;
+  if (!p->inputs || !p->output.primary) { set_error(-2, "matrix equation called without inputs / output"); return nullptr; }
+  const size_t count = b.count;
+  rt_scratch_reset();
+  if (plan->fused_b && jit_on_current_device(plan->fused_b)) {
+    // every element's pointers must be 16-byte aligned: the bases and the strides
+    const void* ptrs[24]; long long strides[24 + 1 + 4]; float alphas[8]; void* dumps[4]; void* args[2 * 24 + 2 + 8 + 2 * 4 + 1]; int na = 0, ns = 0; bool ok = true;
+    for (size_t i = 0; i < plan->fused_inputs.size(); ++i) {
+      const int pos = plan->fused_inputs[i];
+      ptrs[i] = p->inputs[pos].primary; strides[ns++] = b.s_in[pos];
+      if (ptrs[i] && plan->fused_scalar[i]) { ptrs[i] = stage_span(ptrs[i], b.s_in[pos], count, (size_t)typesize(plan->fused_types[i]), false); if (!ptrs[i]) return nullptr; }
+      ok = ok && ptrs[i] && (plan->fused_scalar[i] || ((((size_t)ptrs[i]) | (size_t)b.s_in[pos]) & 15) == 0);
+      args[na++] = (void*)&ptrs[i];
+    }
+    void* outp = p->output.primary;
+    if (plan->out_scalar) { outp = stage_span(outp, b.s_out, count, plan->out_scalar_bytes, true); if (!outp) return nullptr; }
+    else ok = ok && ((((size_t)outp) | (size_t)b.s_out) & 15) == 0;
+    args[na++] = (void*)&outp; strides[ns++] = b.s_out;
+    for (size_t i = 0; i < plan->fused_alphas.size() && ok; ++i) {
+      if (!p->ops_args || !p->ops_args[plan->fused_alphas[i]].primary) { set_error(-2, "matrix equation: op argument %d is NULL", plan->fused_alphas[i]); return nullptr; }
+      alphas[i] = *(const float*)p->ops_args[plan->fused_alphas[i]].primary; args[na++] = (void*)&alphas[i];
+    }
+    for (size_t i = 0; i < plan->fused_dumps.size() && ok; ++i) {
+      const int pos = plan->fused_dumps[i];
+      if (!p->ops_args || !p->ops_args[pos].primary) { set_error(-2, "matrix equation: DUMP destination (op argument %d) is NULL", pos); return nullptr; }
+      dumps[i] = p->ops_args[pos].primary; strides[ns] = stride_of(b.s_ops, b.nops, pos);
+      ok = ok && ((((size_t)dumps[i]) | (size_t)strides[ns]) & 15) == 0; args[na++] = (void*)&dumps[i];
+      ++ns;
+    }
+    if (ok) {
+      long long n = (long long)count;
+      // (strides: inputs, out, then the DUMP destinations -- the generated signature's order behind the pointers and alphas)
+      const size_t nin = plan->fused_inputs.size();
+      for (size_t i = 0; i < nin; ++i) args[na++] = (void*)&strides[i];
+      args[na++] = (void*)&strides[nin];
+      for (size_t i = 0; i < plan->fused_dumps.size(); ++i) args[na++] = (void*)&strides[nin + 1 + i];
+      args[na++] = (void*)&n;
+      // phased: one workgroup per element (the kernel strides over elements beyond 2^20 workgroups); element-wise: units along x, elements along y
+      const unsigned int gx = plan->fused_b_phased ? (unsigned int)std::min<size_t>(count, (size_t)1 << 20) : (unsigned int)((plan->fused_b_total + 255) / 256);
+      const unsigned int gy = plan->fused_b_phased ? 1u : (unsigned int)std::min<size_t>(count, 65535);
+      rt_finish_launch(jit_launch_grid(plan->fused_b, args, gx, gy, rt_stream()), jit_name(plan->fused_b));
+      return jit_name(plan->fused_b);
+    }
+  }
+  // The step chain, each step ONCE for a chunk of elements: intermediates get one slot image per element (slot-major: slot s of element e at
+  // ws + (s * chunk + e) * slot_bytes), the workspace stays below 256 MiB, and the TPP kernels' batch axis (a grid dimension) below 2^16 elements.
+  rt_scratch_reset();
+  std::vector<const char*> in((size_t)plan->ninputs, nullptr);
+  for (int pos = 0; pos < plan->ninputs; ++pos) in[(size_t)pos] = (const char*)p->inputs[pos].primary;
+  std::vector<char> staged((size_t)plan->ninputs, 0);
+  for (const EqnStep& st : plan->steps) for (int c = 0; c < 3; ++c) {
+    const int pos = st.src[c];
+    if (pos == INT32_MIN || pos < 0 || !st.scalar_arg[c] || staged[(size_t)pos] || !in[(size_t)pos]) continue;
+    const int t = c == 0 ? st.args.in0_type : c == 1 ? st.args.in1_type : st.args.in2_type;
+    in[(size_t)pos] = stage_span(in[(size_t)pos], b.s_in[pos], count, (size_t)std::max(1, typesize(t)), false);
+    if (!in[(size_t)pos]) return nullptr;
+    staged[(size_t)pos] = 1;
+  }
+  char* const out_primary = plan->out_scalar ? stage_span(p->output.primary, b.s_out, count, plan->out_scalar_bytes, true) : (char*)p->output.primary;
+  if (!out_primary) return nullptr;
+  const size_t elem_bytes = plan->slot_bytes * (size_t)plan->nslots;
+  size_t chunk = std::min<size_t>(count, 65535);
+  if (elem_bytes > 0) chunk = std::min(chunk, std::max<size_t>(1, ((size_t)256 << 20) / elem_bytes));
+  char* ws = nullptr;
+  if (plan->nslots > 0) { ws = (char*)rt_workspace(elem_bytes * chunk + (plan->has_gemm ? ((size_t)8 << 20) : 0)); if (!ws) return nullptr; }
+  const char* kname = nullptr;
+  int err = 0;
+  for (size_t e0 = 0; e0 < count && err == 0; e0 += chunk) {
+    const size_t ce = std::min(chunk, count - e0);
+    const long long off = (long long)e0;
+    const auto slot_at = [&](int loc) { return ws + plan->slot_bytes * ((size_t)(-loc - 1) * chunk); };
+    for (size_t s = 0; s < plan->steps.size() && err == 0; ++s) {
+      const EqnStep& st = plan->steps[s];
+      MeltwArgs a = st.args;
+      a.nbatch = (unsigned int)ce;
+      const char* src[3] = {nullptr, nullptr, nullptr}; long long bs[3] = {0, 0, 0};
+      for (int c = 0; c < 3; ++c) {
+        if (st.src[c] == INT32_MIN) continue;
+        if (st.src[c] >= 0) { bs[c] = b.s_in[st.src[c]]; src[c] = in[(size_t)st.src[c]] ? in[(size_t)st.src[c]] + off * bs[c] : nullptr; }
+        else { bs[c] = (long long)plan->slot_bytes; src[c] = slot_at(st.src[c]); }
+        if (!src[c]) { set_error(-2, "matrix equation: input %d is NULL", st.src[c]); return nullptr; }
+      }
+      a.in0 = src[0]; a.in1 = src[1]; a.in2 = src[2];
+      a.bs_in0 = bs[0]; a.bs_in1 = bs[1]; a.bs_in2 = bs[2];
+      if (st.out_loc == INT32_MIN) { a.bs_out = b.s_out; a.out = out_primary + off * a.bs_out; }
+      else if (st.out_loc >= 0) { a.bs_out = b.s_in[st.out_loc]; a.out = (char*)p->inputs[st.out_loc].primary + off * a.bs_out; }
+      else { a.bs_out = (long long)plan->slot_bytes; a.out = slot_at(st.out_loc); }
+      if (st.skip_if_in_place && (const char*)a.out == src[0] && a.bs_out == bs[0]) continue;
+      if (st.gemm) {   // a MATMUL / BRGEMM node: the GEMM handle's own strided batch
+        libxsmm_gemm_param gp; std::memset(&gp, 0, sizeof(gp));
+        unsigned long long blocks = 1;
+        gp.a.primary = (void*)src[0]; gp.b.primary = (void*)src[1]; gp.c.primary = a.out;
+        if (st.br_from_op >= 0) {
+          if (!p->ops_args || !p->ops_args[st.br_from_op].tertiary) { set_error(-2, "matrix equation: BRGEMM block count (op argument %d, tertiary) is NULL", st.br_from_op); return nullptr; }
+          blocks = *(const unsigned long long*)p->ops_args[st.br_from_op].tertiary; gp.op.tertiary = &blocks;
+        }
+        rt_workspace_reserve(elem_bytes * chunk);
+        rt_nest(+1);
+        libxsmm_hip_gemm_batch_strided((libxsmm_gemmfunction)st.gemm, &gp, ce, bs[0], bs[1], a.bs_out);
+        rt_nest(-1);
+        rt_workspace_reserve(0);
+        kname = nullptr;
+        continue;
+      }
+      if (st.alpha_from_op >= 0) {
+        if (!p->ops_args || !p->ops_args[st.alpha_from_op].primary) { set_error(-2, "matrix equation: op argument %d is NULL", st.alpha_from_op); return nullptr; }
+        a.scalar_f32 = *(const float*)p->ops_args[st.alpha_from_op].primary;
+      }
+      bool per_element = false;        // a SCATTER head with an index list per element: the TPP kernels share one list across a batch
+      if (st.root_side == 1) {
+        if (!p->output.secondary) { set_error(-2, "matrix equation: the head is a ReLU with bitmask but output.secondary is NULL"); return nullptr; }
+        a.bs_aux = b.s_aux; a.aux_out = (char*)p->output.secondary + off * a.bs_aux;
+      } else if (st.root_side == 2) {
+        if (!p->output.secondary) { set_error(-2, "matrix equation: the head is UNZIP but output.secondary (byte offset of the upper halves) is NULL"); return nullptr; }
+        a.scalar_u64 = *(const unsigned long long*)p->output.secondary;
+      } else if (st.root_side == 3) {
+        if (!p->output.secondary) { set_error(-2, "matrix equation: the head is SCATTER but output.secondary (the index list) is NULL"); return nullptr; }
+        a.aux_out = (char*)p->output.secondary + off * b.s_aux; a.bs_aux = 0; per_element = b.s_aux != 0;
+      }
+      if (st.idx_from_input >= 0) {
+        if (!p->inputs[st.idx_from_input].secondary) { set_error(-2, "matrix equation: GATHER needs its index list in inputs[%d].secondary", st.idx_from_input); return nullptr; }
+        a.aux_in = p->inputs[st.idx_from_input].secondary; a.bs_aux = 0;
+      }
+      if (st.dump_from_op >= 0) {
+        if (!p->ops_args || !p->ops_args[st.dump_from_op].primary) { set_error(-2, "matrix equation: DUMP destination (op argument %d) is NULL", st.dump_from_op); return nullptr; }
+        a.bs_aux = stride_of(b.s_ops, b.nops, st.dump_from_op); a.aux_out = (char*)p->ops_args[st.dump_from_op].primary + off * a.bs_aux;
+      }
+      if (!per_element) { err = launch_meltw(a, rt_stream(), &kname); continue; }
+      for (size_t e = 0; e < ce && err == 0; ++e) {
+        MeltwArgs one = a; const long long k = (long long)e;
+        one.nbatch = 1;
+        one.in0 = a.in0 + k * a.bs_in0; one.in1 = a.in1 ? a.in1 + k * a.bs_in1 : nullptr; one.in2 = a.in2 ? a.in2 + k * a.bs_in2 : nullptr;
+        one.out = a.out + k * a.bs_out; one.aux_out = (char*)a.aux_out + k * b.s_aux;
+        err = launch_meltw(one, rt_stream(), &kname);
+      }
+    }
+    if (err == 0 && e0 + chunk < count) { rt_nest(+1); rt_finish_launch(0, kname ? kname : "meqn"); rt_nest(-1); }     // one launch per chunk; synchronised once at the end
+  }
+  rt_finish_launch(err, kname ? kname : "meqn");
+  return "meqn_tpp_chain";
+}
+
 }  // namespace xamd
 
 using namespace xamd;
@@ -683,6 +895,8 @@ LIBXSMM_API libxsmm_meqn_function libxsmm_dispatch_meqn(libxsmm_blasint idx, lib
   postorder(*e, 0, order);
   EqnPlan* plan = new EqnPlan();
   plan->slot_of.assign(e->nodes.size(), -1);
+  plan->eqn_idx = idx; plan->out_shape = out;
+  for (const EqnNode& nd : e->nodes) if (nd.kind == EQ_ARG) plan->ninputs = std::max(plan->ninputs, nd.in_pos + 1);
   size_t max_elems = 1;
   for (int id : order) max_elems = std::max(max_elems, (size_t)e->nodes[id].ld * (size_t)e->nodes[id].n);
   plan->slot_bytes = (max_elems * 8 + 255) & ~(size_t)255;
@@ -806,11 +1020,12 @@ LIBXSMM_API libxsmm_meqn_function libxsmm_dispatch_meqn(libxsmm_blasint idx, lib
   if (rt_jit_mode() != 0) {     // element-wise trees: one generated kernel instead of one launch per node
     std::string src, fname; long long total = 0;
     EqnPlan probe;
-    if (generate_fused(*e, out, idx, src, fname, probe, total)) {
+    if (generate_fused(*e, out, idx, false, src, fname, probe, total)) {
       std::string why;
       plan->fused = jit_compile(src, fname, total, 16, &why);
       if (!plan->fused && std::getenv("LIBXSMM_HIP_JIT_VERBOSE")) std::fprintf(stderr, "libxsmm_amd: generated equation kernel did not compile: %s\n%s\n", why.c_str(), src.c_str());
-      if (plan->fused) { plan->fused_inputs = probe.fused_inputs; plan->fused_scalar = probe.fused_scalar; plan->fused_alphas = probe.fused_alphas; plan->fused_dumps = probe.fused_dumps; }
+      if (plan->fused) { plan->fused_inputs = probe.fused_inputs; plan->fused_scalar = probe.fused_scalar; plan->fused_alphas = probe.fused_alphas; plan->fused_dumps = probe.fused_dumps;
+                         plan->fused_types = probe.fused_types; }
     }
   }
   const void* h = rt_new_meqn_handle(plan);

@@ -2198,6 +2198,16 @@ LIBXSMM_API void libxsmm_hip_meltw_ternary_batch_strided(libxsmm_meltwfunction_t
   KernelCtx* c = batch_ctx((const void*)kernel, K_MELTW); if (!c || !param || count == 0) return;
   BatchSpec b; b.count = count; b.s[0] = s0; b.s[1] = s1; b.s[2] = s2; b.s[3] = so; run_meltw(c, param, b);
 }
+LIBXSMM_API void libxsmm_hip_meqn_batch_strided(libxsmm_meqn_function kernel, const libxsmm_meqn_param* param, size_t count,
+  int ninputs, const long long* stride_inputs, long long stride_output, long long stride_output_aux, int nops_args, const long long* stride_ops_args) {
+  KernelCtx* c = batch_ctx((const void*)kernel, K_MEQN); if (!c || !param || count == 0) return;
+  const MeqnBatch b{count, ninputs, stride_inputs, stride_output, stride_output_aux, nops_args, stride_ops_args};
+  if (!meqn_batch_prepare(c->eqn, b)) return;         // validation and the batched kernel come first: a dry run (no device) exercises both
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  if (const char* kname = run_meqn_batch(c->eqn, param, b)) c->kname_batched = kname;
+}
 // ---- multi-device launch from ONE host thread (the reference's scale-out axis is the caller's loop,
 // samples/xgemm/gemm_kernel.c:4063-4066) --------------------------------------------------------------------------------------------------------
 // Every shard has a context of its own on the calling thread -- device, a non-blocking stream there, staging scratch, partial-result workspaces -- that is
