@@ -1386,6 +1386,227 @@ __global__ __launch_bounds__(256) void reduce_combine_kernel(MeltwArgs p, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// f64 reductions (in0 = out = F64): the designs of the f32 kernels above with double accumulators and the steps of the reference's f64 branch
+// [ref: mateltwise ref :1143-1295], where MAX(a, b) = a < b ? b : a, MIN(a, b) = a < b ? a : b, ABS(a) = 0 <= a ? a : -a:
+//   over rows     acc starts at the column's first element; acc = MAX(acc, x), MIN(acc, x), MAX(ABS(acc), ABS(x));
+//   over columns  acc starts at -FLT_MAX, FLT_MAX, 0 (the float bounds, widened); acc = MAX(x, acc), MIN(x, acc), ABSMAX: MAX(ABS(x), acc).
+// Partial results (lanes, column slices, column chunks) are folded with the same step.  Slices and chunks are CONTIGUOUS column ranges folded in
+// column order, so MAX / MIN / ABSMAX over columns equal the serial loop bit for bit (ties included) for inputs without NaN; over rows they equal it in
+// value (a lane tree may keep the other zero of a +0 / -0 tie).  Sums: serial order in the general kernel and the one-slice column form, else
+// slice / chunk / lane partial sums added in a fixed order -- deterministic run to run.  The x^2 sums are stored (the reference's loop leaves zeros).
+// ------------------------------------------------------------------------------------------------
+enum { RO_ADD = 0, RO_MAX = 1, RO_MIN = 2, RO_ABSMAX = 3 };
+__device__ __forceinline__ int red64_op(int type) {
+  return type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX ? RO_MAX : type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN ? RO_MIN
+       : type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_ABSMAX ? RO_ABSMAX : RO_ADD;
+}
+__device__ __forceinline__ double red64_abs(double a) { return (0.0 <= a) ? a : -a; }
+__device__ __forceinline__ double red64_row(int op, double acc, double x) {         // one step of the loop over rows
+  switch (op) {
+    case RO_ADD: return acc + x;
+    case RO_MAX: return (acc < x) ? x : acc;
+    case RO_MIN: return (acc < x) ? acc : x;
+    default: { const double a = red64_abs(acc), b = red64_abs(x); return (a < b) ? b : a; }
+  }
+}
+__device__ __forceinline__ double red64_col(int op, double acc, double x) {         // one step of the loop over columns
+  switch (op) {
+    case RO_ADD: return acc + x;
+    case RO_MAX: return (x < acc) ? acc : x;
+    case RO_MIN: return (x < acc) ? x : acc;
+    default: { const double b = red64_abs(x); return (b < acc) ? acc : b; }
+  }
+}
+__device__ __forceinline__ double red64_col_start(int op) { return op == RO_MAX ? -(double)3.402823466e+38f : op == RO_MIN ? (double)3.402823466e+38f : 0.0; }
+__device__ __forceinline__ void red64_store(GM double* out, GM double* out2, long long i, bool add_init, bool want_x, bool want_x2, double sx, double sx2) {
+  if (add_init) { if (want_x) sx += out[i]; if (want_x2) sx2 += out2[i]; }
+  if (want_x) out[i] = sx;
+  if (want_x2) out2[i] = sx2;
+}
+#define RED64_PROLOGUE                                                                                                                            \
+  const bool rows = (p.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS) != 0;                                                                        \
+  const int type = p.type, op = red64_op(type);                                                                                                   \
+  const bool want_x = type != LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X2_OP_ADD;                                                                          \
+  const bool want_x2 = type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X2_OP_ADD || type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_X2_OP_ADD;                  \
+  const bool add_init = op == RO_ADD && (p.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_INIT_ACC) != 0;                                                \
+  GM const double* in = (GM const double*)((gcptr)p.in0 + (long long)blockIdx.y * p.bs_in0);                                                      \
+  GM double* out = (GM double*)((gptr)p.out + (long long)blockIdx.y * p.bs_out);                                                                   \
+  GM double* out2 = (want_x && want_x2) ? out + (rows ? (long long)p.n : (long long)p.ldo) : out;
+
+// general form: any m, ld and alignment -- one wave per column (xor-shuffle tree) or one thread per row (columns in order)
+__global__ __launch_bounds__(256) void reduce_f64_kernel(MeltwArgs p) {
+  RED64_PROLOGUE
+  if (rows) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + wave;
+    if (j >= p.n) return;
+    GM const double* col = in + (long long)j * p.ldi;
+    double sx = op == RO_ADD ? 0.0 : col[0], sx2 = 0.0;
+    for (int i = lane; i < p.m; i += 64) { const double x = col[i]; sx = red64_row(op, sx, x); sx2 += x * x; }
+    for (int off = 32; off > 0; off >>= 1) { sx = red64_row(op, sx, __shfl_xor(sx, off)); if (want_x2) sx2 += __shfl_xor(sx2, off); }
+    if (lane == 0) red64_store(out, out2, j, add_init, want_x, want_x2, sx, sx2);
+  } else {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.m) return;
+    double sx = red64_col_start(op), sx2 = 0.0;
+    for (int j = 0; j < p.n; ++j) { const double x = in[i + (long long)j * p.ldi]; sx = red64_col(op, sx, x); sx2 += x * x; }
+    red64_store(out, out2, i, add_init, want_x, want_x2, sx, sx2);
+  }
+}
+
+// Vector form (m % 2 == 0, ldi % 2 == 0, 16-byte aligned input): every lane loads 16 bytes (two doubles) per access.
+//   REDUCE_ROWS: a group of G = min(64, pow2(m/2)) lanes owns a column (CPG columns per trip when a column is one vector per lane), folded with shuffles.
+//   REDUCE_COLS: a thread owns 2 consecutive rows of 16 row groups and one of `slices` contiguous column ranges; the slices are folded in order through
+//     LDS.  partial != NULL: the two-pass form, blockIdx.z owns columns [z*chunk, (z+1)*chunk) and writes partial[z][x / x2][m].
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+template <int CPG = 1>
+__global__ __launch_bounds__(256) void reduce_vec_f64_kernel(MeltwArgs p, int G, int slices, int chunk, double* partial) {
+  __shared__ double part[2][16][16][2];
+  RED64_PROLOGUE
+  const int m2 = p.m / 2;
+  const auto ld2 = [&](long long idx) { return *(GM const f64x2*)(in + idx); };
+  if (rows) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane % G, cpw = 64 / G;
+    if constexpr (CPG > 1) {
+      const int j0 = ((blockIdx.x * 4 + wave) * cpw + lane / G) * CPG;
+      f64x2 x[CPG];
+#pragma unroll
+      for (int u = 0; u < CPG; ++u) {
+        if (j0 + u < p.n && l < m2) x[u] = ld2(2ll * l + (long long)(j0 + u) * p.ldi);
+        else { x[u][0] = 0.0; x[u][1] = 0.0; }
+      }
+#pragma unroll
+      for (int u = 0; u < CPG; ++u) {
+        double sx = op == RO_ADD ? 0.0 : __shfl(x[u][0], lane - l), sx2 = 0.0;     // MAX / MIN / ABSMAX: the column's first element, from lane 0 of the group
+        if (l < m2) { sx = red64_row(op, red64_row(op, sx, x[u][0]), x[u][1]); sx2 += x[u][0] * x[u][0]; sx2 += x[u][1] * x[u][1]; }
+        for (int off = G >> 1; off > 0; off >>= 1) { sx = red64_row(op, sx, __shfl_xor(sx, off)); if (want_x2) sx2 += __shfl_xor(sx2, off); }
+        if (l == 0 && j0 + u < p.n) red64_store(out, out2, j0 + u, add_init, want_x, want_x2, sx, sx2);
+      }
+      return;
+    }
+    const int j = (blockIdx.x * 4 + wave) * cpw + lane / G;
+    double sx = 0.0, sx2 = 0.0;
+    if (j < p.n) {
+      GM const double* col = in + (long long)j * p.ldi;
+      if (op != RO_ADD) sx = col[0];
+      int i2 = l;
+      for (; i2 + 15 * G < m2; i2 += 16 * G) {        // sixteen vectors (16 KiB per wave) in flight, folded in the order of the plain loop
+        f64x2 x[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) x[u] = ld2(2ll * (i2 + u * G) + (long long)j * p.ldi);
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) { sx = red64_row(op, sx, x[u][e]); sx2 += x[u][e] * x[u][e]; }
+      }
+      for (; i2 < m2; i2 += G) {
+        const f64x2 x = ld2(2ll * i2 + (long long)j * p.ldi);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) { sx = red64_row(op, sx, x[e]); sx2 += x[e] * x[e]; }
+      }
+    }
+    for (int off = G >> 1; off > 0; off >>= 1) { sx = red64_row(op, sx, __shfl_xor(sx, off)); if (want_x2) sx2 += __shfl_xor(sx2, off); }
+    if (l == 0 && j < p.n) red64_store(out, out2, j, add_init, want_x, want_x2, sx, sx2);
+  } else {
+    const int rg_l = threadIdx.x % 16, sl = threadIdx.x / 16;
+    const int rg = blockIdx.x * 16 + rg_l;
+    const double s0 = red64_col_start(op);
+    double sx[2] = {s0, s0}, sx2[2] = {0.0, 0.0};
+    const int jbeg = partial ? (int)blockIdx.z * chunk : 0, jend = partial ? ((jbeg + chunk < p.n) ? jbeg + chunk : p.n) : p.n;
+    const int per = (jend - jbeg + slices - 1) / slices;
+    const int sbeg = jbeg + sl * per, send = (sbeg + per < jend) ? sbeg + per : jend;
+    if (rg < m2 && sl < slices) {
+      int j = sbeg;
+      for (; j + 15 < send; j += 16) {          // sixteen columns in flight per thread, folded in column order
+        f64x2 x[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) x[u] = ld2(2ll * rg + (long long)(j + u) * p.ldi);
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) { sx[e] = red64_col(op, sx[e], x[u][e]); sx2[e] += x[u][e] * x[u][e]; }
+      }
+      for (; j < send; ++j) {
+        const f64x2 x = ld2(2ll * rg + (long long)j * p.ldi);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) { sx[e] = red64_col(op, sx[e], x[e]); sx2[e] += x[e] * x[e]; }
+      }
+    }
+    if (slices > 1) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) { part[0][sl][rg_l][e] = sx[e]; part[1][sl][rg_l][e] = sx2[e]; }
+      __syncthreads();
+      if (sl != 0) return;
+      for (int s2 = 1; s2 < slices; ++s2)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) { sx[e] = red64_col(op, sx[e], part[0][s2][rg_l][e]); sx2[e] += part[1][s2][rg_l][e]; }
+    } else if (sl != 0) return;
+    if (rg >= m2) return;
+    if (partial) {
+      GM double* px = (GM double*)partial + ((long long)blockIdx.z * 2) * p.m + 2ll * rg;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) { px[e] = sx[e]; if (want_x2) px[p.m + e] = sx2[e]; }
+      return;
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) red64_store(out, out2, 2ll * rg + e, add_init, want_x, want_x2, sx[e], sx2[e]);
+  }
+}
+
+// second pass of the two-pass f64 column form: partial[z][x / x2][m] folded in chunk order z = 0, 1, ... (sixteen chunks in flight per thread)
+__global__ __launch_bounds__(256) void reduce_combine_f64_kernel(MeltwArgs p, const double* partial, int nchunks) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.m) return;
+  RED64_PROLOGUE
+  (void)in;
+  GM const double* px = (GM const double*)partial + i;
+  double a = px[0], b = want_x2 ? px[p.m] : 0.0;
+  int z = 1;
+  for (; z + 15 < nchunks; z += 16) {
+    double x[16], x2[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { x[u] = px[(long long)(z + u) * 2 * p.m]; x2[u] = want_x2 ? px[((long long)(z + u) * 2 + 1) * p.m] : 0.0; }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) { a = red64_col(op, a, x[u]); b += x2[u]; }
+  }
+  for (; z < nchunks; ++z) { a = red64_col(op, a, px[(long long)z * 2 * p.m]); b += want_x2 ? px[((long long)z * 2 + 1) * p.m] : 0.0; }
+  red64_store(out, out2, i, add_init, want_x, want_x2, a, b);
+}
+
+// f64 form of reduce_cols_listed_kernel: listed columns (REDUCE_COLS_IDX_OP_ADD / MAX / MIN) and the column MAX / ABSMAX / MIN that record the argop,
+// one thread per row, the columns in the caller's order; a later equal extremum wins (>= / <=), an all-NaN row keeps its old index [ref: :1225-1280]
+__global__ __launch_bounds__(256) void reduce_cols_listed_f64_kernel(MeltwArgs p) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.m) return;
+  const unsigned int b = blockIdx.y;
+  GM const double* in = (GM const double*)((gcptr)p.in0 + (long long)b * p.bs_in0);
+  GM double* out = (GM double*)((gptr)p.out + (long long)b * p.bs_out);
+  const bool idx4 = (p.flags & LIBXSMM_MELTW_FLAG_UNARY_IDX_SIZE_4BYTES) != 0, record = (p.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_RECORD_ARGOP) != 0;
+  const bool listed = p.type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_COLS_IDX_OP_ADD || p.type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_COLS_IDX_OP_MAX || p.type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_COLS_IDX_OP_MIN;
+  const int op = (p.type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_COLS_IDX_OP_ADD) ? RO_ADD
+               : (p.type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_COLS_IDX_OP_MAX || p.type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) ? RO_MAX
+               : (p.type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_ABSMAX) ? RO_ABSMAX : RO_MIN;
+  const unsigned long long n_cols = listed ? p.scalar_u64 : (unsigned long long)p.n;
+  GM const unsigned int* idx32 = (GM const unsigned int*)((gcptr)p.aux_in + (long long)b * p.bs_aux);
+  GM const unsigned long long* idx64 = (GM const unsigned long long*)((gcptr)p.aux_in + (long long)b * p.bs_aux);
+  double acc = red64_col_start(op);
+  unsigned long long arg = 0; bool found = false;
+  for (unsigned long long jj = 0; jj < n_cols; ++jj) {
+    const unsigned long long j = listed ? (idx4 ? (unsigned long long)idx32[jj] : idx64[jj]) : jj;     // wave-uniform: one scalar load
+    double x = in[(long long)i + (long long)j * p.ldi];
+    if (op == RO_ADD) { acc += x; continue; }
+    if (!record) { acc = red64_col(op, acc, x); continue; }
+    if (op == RO_ABSMAX) x = red64_abs(x);
+    if (op == RO_MIN ? (x <= acc) : (x >= acc)) { acc = x; arg = j; found = true; }
+  }
+  out[i] = acc;
+  if (record && found) {
+    if (idx4) ((GM unsigned int*)p.aux_out)[i] = (unsigned int)arg; else ((GM unsigned long long*)p.aux_out)[i] = arg;
+  }
+}
+#undef RED64_PROLOGUE
+
+// ------------------------------------------------------------------------------------------------
 // host-side selection
 // ------------------------------------------------------------------------------------------------
 
@@ -1566,7 +1787,9 @@ bool meltw_supported(const libxsmm_meltw_descriptor& d) {
         t == LIBXSMM_MELTW_TYPE_UNARY_GATHER || t == LIBXSMM_MELTW_TYPE_UNARY_SCATTER) return sz == 1 || sz == 2 || sz == 4 || sz == 8;
     if (t == LIBXSMM_MELTW_TYPE_UNARY_DROPOUT || t == LIBXSMM_MELTW_TYPE_UNARY_DROPOUT_INV)      // no broadcasts; 16 rows per draw
       return is_tpp_float(d.in0_type) && is_tpp_float(d.out_type) && !(d.flags & (LIBXSMM_MELTW_FLAG_UNARY_BCAST_ROW | LIBXSMM_MELTW_FLAG_UNARY_BCAST_COL | LIBXSMM_MELTW_FLAG_UNARY_BCAST_SCALAR | LIBXSMM_MELTW_FLAG_UNARY_STOCHASTIC_ROUND));
-    if (is_reduce_cols_idx_type(t)) return is_tpp_float(d.in0_type) && is_tpp_float(d.out_type);
+    // all-f64 reductions compute in double; the reference's f64 branch tests only the in / out types (comp F64 or F32) [ref: :1143]
+    const bool f64_reduce = f64 && (d.comp_type == LIBXSMM_DATATYPE_F64 || d.comp_type == LIBXSMM_DATATYPE_F32);
+    if (is_reduce_cols_idx_type(t)) return f64_reduce || (is_tpp_float(d.in0_type) && is_tpp_float(d.out_type));
     if (t == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_TO_SCALAR_OP_ADD)                                  // [ref: :2097-2116] f64 only when input, output and compute all are
       return (f64 && d.comp_type == LIBXSMM_DATATYPE_F64) || (is_tpp_float(d.in0_type) && is_tpp_float(d.out_type));
     if (t == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_ADD_NCNC_FORMAT)                              // [ref: :2118-2141] m = bc, n = bn, ldi = C, ldo = N
@@ -1574,9 +1797,9 @@ bool meltw_supported(const libxsmm_meltw_descriptor& d) {
     if (t == LIBXSMM_MELTW_TYPE_UNARY_DECOMP_FP32_TO_BF16X2 || t == LIBXSMM_MELTW_TYPE_UNARY_DECOMP_FP32_TO_BF16X3)      // [ref: :2437-2470]
       return d.in0_type == LIBXSMM_DATATYPE_F32 && d.out_type == LIBXSMM_DATATYPE_BF16;
     if (is_reduce_type(t) && (d.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_RECORD_ARGOP))       // recorded for MAX / ABSMAX / MIN over columns [ref: :1376-1424]
-      return is_tpp_float(d.in0_type) && is_tpp_float(d.out_type) && !(d.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS) &&
+      return (f64_reduce || (is_tpp_float(d.in0_type) && is_tpp_float(d.out_type))) && !(d.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS) &&
              (t == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX || t == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN || t == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_ABSMAX);
-    if (is_reduce_type(t)) return is_tpp_float(d.in0_type) && is_tpp_float(d.out_type);
+    if (is_reduce_type(t)) return f64_reduce || (is_tpp_float(d.in0_type) && is_tpp_float(d.out_type));
     if (t == LIBXSMM_MELTW_TYPE_UNARY_UNZIP) return d.in0_type == LIBXSMM_DATATYPE_F32 && (d.out_type == LIBXSMM_DATATYPE_BF16 || d.out_type == LIBXSMM_DATATYPE_U16 || d.out_type == LIBXSMM_DATATYPE_I16);
     const auto is_qint = [](int x) { return x == LIBXSMM_DATATYPE_I8 || x == LIBXSMM_DATATYPE_I16 || x == LIBXSMM_DATATYPE_I32; };
     if (t == LIBXSMM_MELTW_TYPE_UNARY_QUANT && d.out_type == LIBXSMM_DATATYPE_NVFP4X2)      // 16-row blocks, E4M3 scales
@@ -1727,6 +1950,41 @@ int launch_stochastic_bf8(const MeltwArgs& a, void* stream) {
   return (int)hipGetLastError();
 }
 
+// the f64 reductions: the f32 launch's choices (vector form when the input allows 16-byte accesses, the short-column form, two passes over one big
+// matrix's columns) with two doubles where the f32 form has four floats
+static void launch_reduce_f64(const MeltwArgs& a, hipStream_t st, const char** name) {
+  const bool rows = (a.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS) != 0;
+  if (!(a.m % 2 == 0 && a.ldi % 2 == 0 && (((size_t)a.in0 | (size_t)a.bs_in0) % 16) == 0 && a.nbatch < 65536)) {
+    const unsigned int gx = rows ? (unsigned int)((a.n + 3) / 4) : (unsigned int)((a.m + 255) / 256);
+    hipLaunchKernelGGL(reduce_f64_kernel, dim3(gx, a.nbatch), dim3(256), 0, st, a);
+    if (name) *name = "reduce_f64_kernel";
+    return;
+  }
+  const int m2 = a.m / 2;
+  int G = 1; while (G < 64 && G < m2) G <<= 1;
+  const int slices = (!rows && a.n >= 256) ? 16 : 1;
+  const unsigned int gx = rows ? (unsigned int)((a.n + 4 * (64 / G) - 1) / (4 * (64 / G))) : (unsigned int)((m2 + 15) / 16);
+  int nchunks = 1;
+  if (!rows && a.ws && a.nbatch == 1 && gx < 512) {
+    nchunks = (int)std::min<long long>(128, std::min<long long>(a.n / 64, 512 / (gx ? gx : 1)));
+    if ((size_t)nchunks * 2 * (size_t)a.m * sizeof(double) > a.ws_bytes) nchunks = 1;
+  }
+  if (rows && m2 <= G && a.n >= 64) {       // short columns: four per lane group and trip
+    const unsigned int gx4 = (unsigned int)((a.n + 16 * (64 / G) - 1) / (16 * (64 / G)));
+    hipLaunchKernelGGL((reduce_vec_f64_kernel<4>), dim3(gx4, a.nbatch), dim3(256), 0, st, a, G, slices, 0, (double*)nullptr);
+    if (name) *name = "reduce_vec_f64_kernel";
+  } else if (nchunks > 1) {
+    const int chunk = (a.n + nchunks - 1) / nchunks;
+    nchunks = (a.n + chunk - 1) / chunk;
+    hipLaunchKernelGGL((reduce_vec_f64_kernel<1>), dim3(gx, 1, nchunks), dim3(256), 0, st, a, G, slices, chunk, (double*)a.ws);
+    hipLaunchKernelGGL(reduce_combine_f64_kernel, dim3((unsigned int)((a.m + 255) / 256)), dim3(256), 0, st, a, (const double*)a.ws, nchunks);
+    if (name) *name = "reduce_vec_f64_kernel+combine";
+  } else {
+    hipLaunchKernelGGL((reduce_vec_f64_kernel<1>), dim3(gx, a.nbatch), dim3(256), 0, st, a, G, slices, 0, (double*)nullptr);
+    if (name) *name = "reduce_vec_f64_kernel";
+  }
+}
+
 int launch_meltw(const MeltwArgs& a, void* stream, const char** name) {
   hipStream_t st = (hipStream_t)stream;
   const bool listed = a.operation == LIBXSMM_MELTW_OPERATION_UNARY && is_reduce_cols_idx_type(a.type);      // the shape's n does not matter there (the reference's driver passes 0)
@@ -1736,8 +1994,9 @@ int launch_meltw(const MeltwArgs& a, void* stream, const char** name) {
   if (a.nbatch == 0 || a.m <= 0 || (a.n <= 0 && !n_by_call)) { if (name) *name = "(empty)"; return 0; }
   const int sz = payload_size(a.in0_type);
   if (listed) {
-    hipLaunchKernelGGL(reduce_cols_listed_kernel, dim3((unsigned int)((a.m + 255) / 256), a.nbatch), dim3(256), 0, st, a);
-    if (name) *name = "reduce_cols_listed_kernel";
+    if (a.in0_type == LIBXSMM_DATATYPE_F64) hipLaunchKernelGGL(reduce_cols_listed_f64_kernel, dim3((unsigned int)((a.m + 255) / 256), a.nbatch), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(reduce_cols_listed_kernel, dim3((unsigned int)((a.m + 255) / 256), a.nbatch), dim3(256), 0, st, a);
+    if (name) *name = a.in0_type == LIBXSMM_DATATYPE_F64 ? "reduce_cols_listed_f64_kernel" : "reduce_cols_listed_kernel";
     return (int)hipGetLastError();
   }
   if (ew8_ok(a)) {
@@ -1890,8 +2149,11 @@ int launch_meltw(const MeltwArgs& a, void* stream, const char** name) {
         if (name) *name = "gather_scatter_kernel";
       }
     } else if (is_reduce_cols_idx_type(a.type) || (is_reduce_type(a.type) && (a.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_RECORD_ARGOP))) {
-      hipLaunchKernelGGL(reduce_cols_listed_kernel, dim3((unsigned int)((a.m + 255) / 256), a.nbatch), dim3(256), 0, st, a);
-      if (name) *name = "reduce_cols_listed_kernel";
+      if (a.in0_type == LIBXSMM_DATATYPE_F64) hipLaunchKernelGGL(reduce_cols_listed_f64_kernel, dim3((unsigned int)((a.m + 255) / 256), a.nbatch), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(reduce_cols_listed_kernel, dim3((unsigned int)((a.m + 255) / 256), a.nbatch), dim3(256), 0, st, a);
+      if (name) *name = a.in0_type == LIBXSMM_DATATYPE_F64 ? "reduce_cols_listed_f64_kernel" : "reduce_cols_listed_kernel";
+    } else if (is_reduce_type(a.type) && a.in0_type == LIBXSMM_DATATYPE_F64) {
+      launch_reduce_f64(a, st, name);
     } else if (is_reduce_type(a.type)) {
       const bool rows = (a.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS) != 0;
       const bool bf = a.in0_type == LIBXSMM_DATATYPE_BF16;

@@ -789,7 +789,7 @@ void run_meltw(KernelCtx* k, const void* param, const BatchSpec& b) {
     a.bs_in0 = b.s[0]; a.bs_out = b.s[1]; a.bs_aux = b.s[2];
     const int t = d.param;
     if ((d.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_COLS) && d.n >= 2048 && b.count == 1) {   // one big matrix reduced over its columns: two passes
-      a.ws_bytes = (size_t)128 * 2 * (size_t)d.m * sizeof(float); a.ws = workspace(a.ws_bytes);
+      a.ws_bytes = (size_t)128 * 2 * (size_t)d.m * (d.in0_type == LIBXSMM_DATATYPE_F64 ? sizeof(double) : sizeof(float)); a.ws = workspace(a.ws_bytes);   // partials in the accumulator's type
     }
     if (d.flags & LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT) {       // a missing mask pointer would be a device fault: say so instead
       const bool fwd = t == LIBXSMM_MELTW_TYPE_UNARY_RELU || t == LIBXSMM_MELTW_TYPE_UNARY_LEAKY_RELU || t == LIBXSMM_MELTW_TYPE_UNARY_ELU;

@@ -443,20 +443,21 @@ def meltw_gather_cols(api, m=4096, n=8192, src_cols=16384):
     return w
 
 
-def meltw_reduce(api, rows, m=4096, n=8192, batch=1):
-    """REDUCE_X_OP_ADD over rows (one result per column) or over columns (one result per row)."""
+def meltw_reduce(api, rows, m=4096, n=8192, batch=1, dt=DT.F32):
+    """REDUCE_X_OP_ADD over rows (one result per column) or over columns (one result per row); f32 or all-f64."""
     flag = UNARY_FLAG.REDUCE_ROWS if rows else UNARY_FLAG.REDUCE_COLS
     res = n if rows else m
-    h = api.dispatch_meltw_unary(UNARY.REDUCE_X_OP_ADD, capi.UnaryShape(m, n, m, res, DT.F32, DT.F32, DT.F32), flag)
+    es, tn = (8, "f64") if dt == DT.F64 else (4, "f32")
+    h = api.dispatch_meltw_unary(UNARY.REDUCE_X_OP_ADD, capi.UnaryShape(m, n, m, res, dt, dt, dt), flag)
     assert h
-    ns = nsets_for(batch * m * n * 4)
-    X = [rnd(batch * m * n) for _ in range(ns)]
-    Y = [torch.zeros(batch * res, device=DEV) for _ in range(ns)]
+    ns = nsets_for(batch * m * n * es)
+    X = [rnd(batch * m * n) if es == 4 else torch.randn(batch * m * n, device=DEV, dtype=torch.float64) for _ in range(ns)]
+    Y = [torch.zeros(batch * res, device=DEV, dtype=torch.float32 if es == 4 else torch.float64) for _ in range(ns)]
     ps = []
     for s in range(ns):
         q = capi.UnaryParam(); q.in_.primary, q.out.primary = X[s].data_ptr(), Y[s].data_ptr(); ps.append(q)
-    step = (lambda s: capi.Api.call(h, ps[s])) if batch == 1 else (lambda s: api.hip_meltw_unary_batch_strided(h, C.byref(ps[s]), batch, m * n * 4, res * 4, 0))
-    w = Work(api, f"meltw unary REDUCE_X_OP_ADD over {'rows' if rows else 'cols'} f32 {m}x{n} x{batch}", float(batch * m * n), float(batch * (m * n + res) * 4), ns, step)
+    step = (lambda s: capi.Api.call(h, ps[s])) if batch == 1 else (lambda s: api.hip_meltw_unary_batch_strided(h, C.byref(ps[s]), batch, m * n * es, res * es, 0))
+    w = Work(api, f"meltw unary REDUCE_X_OP_ADD over {'rows' if rows else 'cols'} {tn} {m}x{n} x{batch}", float(batch * m * n), float(batch * (m * n + res) * es), ns, step)
     w.keep = (X, Y, ps)
     return w
 
@@ -582,7 +583,16 @@ def main():
                    lambda: meltw_big(api, UNARY.IDENTITY, "IDENTITY f32->bf16", out_dt=DT.BF16),
                    lambda: meltw_big(api, UNARY.TRANSFORM_NORM_TO_NORMT, "TRANSPOSE f32"),
                    lambda: meltw_big(api, UNARY.TRANSFORM_NORM_TO_VNNI2, "NORM_TO_VNNI2 bf16", in_dt=DT.BF16, out_dt=DT.BF16),
-                   lambda: meltw_gather_cols(api), lambda: meltw_reduce(api, True), lambda: meltw_reduce(api, False), lambda: meltw_reduce(api, True, 64, 1024, 512), lambda: meltw_reduce(api, False, 64, 1024, 512)]
+                   lambda: meltw_gather_cols(api), lambda: meltw_reduce(api, True), lambda: meltw_reduce(api, False), lambda: meltw_reduce(api, True, 64, 1024, 512), lambda: meltw_reduce(api, False, 64, 1024, 512),
+                   # f64 next to f32 on the same footprint: 4096 x 4096 f64 = 128 MiB = 4096 x 8192 f32
+                   lambda: meltw_reduce(api, True, 4096, 4096, dt=DT.F64), lambda: meltw_reduce(api, False, 4096, 4096, dt=DT.F64),
+                   lambda: meltw_reduce(api, True, 64, 1024, 512, dt=DT.F64), lambda: meltw_reduce(api, False, 64, 1024, 512, dt=DT.F64)]
+    if "reduce" in only:     # the f32 and f64 reduction rows alone, alternated (f32, f64, f32, f64) in one run
+        for _ in range(2):
+            makers += [lambda: meltw_reduce(api, True), lambda: meltw_reduce(api, True, 4096, 4096, dt=DT.F64),
+                       lambda: meltw_reduce(api, False), lambda: meltw_reduce(api, False, 4096, 4096, dt=DT.F64),
+                       lambda: meltw_reduce(api, True, 64, 1024, 512), lambda: meltw_reduce(api, True, 64, 1024, 512, dt=DT.F64),
+                       lambda: meltw_reduce(api, False, 64, 1024, 512), lambda: meltw_reduce(api, False, 64, 1024, 512, dt=DT.F64)]
     for mk in makers:
         try:
             ws = mk()
