@@ -202,6 +202,7 @@ LIBXSMM_API int libxsmm_hip_gemm_ext_batch_strided_sharded(libxsmm_gemmfunction_
  * (granule = whole lane tiles), create one kernel per non-empty shard ON that shard's device (devices[s], NULL: s % device_count; a device may appear
  * several times -- virtual shards), and keep them together.  Every shard's operands live on its device in the shard's OWN compact layout:
  *   packed CSR / CSC (axis = the packed width P):   B [K][N][P_s], C [M][N][P_s] (CSR, A sparse);  A [M][K][P_s], C [M][N][P_s] (CSC, B sparse)
+ *                                                    -- compact only: NULL unless ldc == n and ldb == n (A sparse) or lda == k (B sparse)
  *   BCSC (axis = the M-blocks = shape.m, as the creator takes them): A and C of the shard's M-blocks; the block-sparse B is replicated by the caller
  *   FsSpMDM (axis = N):                              B [K][N_s], C [M][N_s]  (leading dimensions = N_s)
  * libxsmm_hip_sharded_launch: shard_params[i] (i = 0 .. shards - 1, non-empty shards in order) holds shard i's operand pointers exactly as the plain kernel

@@ -147,13 +147,16 @@ libxsmm_hip_sharded_kernel* build_sharded(libxsmm_hip_sharded_kernel::Kind kind,
 extern "C" {
 LIBXSMM_API libxsmm_hip_sharded_kernel* libxsmm_hip_create_packed_spgemm_csr_sharded(libxsmm_gemm_shape shape, libxsmm_bitfield flags, libxsmm_bitfield prefetch,
   libxsmm_blasint packed_width, const unsigned int* row_ptr, const unsigned int* column_idx, const void* values, int nshards, const int* devices) {
-  if (packed_width <= 0) return nullptr;
+  // every shard writes C as [M][ldc][P_s] but the gather moves M * N rows of P_s: only the compact layout is shardable
+  // (A sparse: ldb = ldc = n; the B-sparse form of this creator, ldb = 0: lda = k, ldc = n)
+  if (packed_width <= 0 || shape.ldc != shape.n || (shape.lda == 0 ? shape.ldb != shape.n : (shape.ldb != 0 || shape.lda != shape.k))) return nullptr;
   return build_sharded(libxsmm_hip_sharded_kernel::CSR, (size_t)packed_width, kShardGranule, (size_t)LIBXSMM_TYPESIZE(shape.out_type), (size_t)shape.m * (size_t)shape.n, nshards, devices,
     [&](libxsmm_hip_sharded_kernel::Shard& sh, size_t width) { sh.kernel = libxsmm_create_packed_spgemm_csr(shape, flags, prefetch, (libxsmm_blasint)width, row_ptr, column_idx, values); return sh.kernel != nullptr; });
 }
 LIBXSMM_API libxsmm_hip_sharded_kernel* libxsmm_hip_create_packed_spgemm_csc_sharded(libxsmm_gemm_shape shape, libxsmm_bitfield flags, libxsmm_bitfield prefetch,
   libxsmm_blasint packed_width, const unsigned int* column_ptr, const unsigned int* row_idx, const void* values, int nshards, const int* devices) {
   if (packed_width <= 0 || shape.ldc == 0) return nullptr;       // (ldc == 0: C sparse -- the packed axis is a REDUCTION there, not a batch of independent columns: not shardable by this call)
+  if (shape.lda != shape.k || shape.ldc != shape.n) return nullptr;  // the compact per-shard layout only, as for the CSR form
   return build_sharded(libxsmm_hip_sharded_kernel::CSC, (size_t)packed_width, kShardGranule, (size_t)LIBXSMM_TYPESIZE(shape.out_type), (size_t)shape.m * (size_t)shape.n, nshards, devices,
     [&](libxsmm_hip_sharded_kernel::Shard& sh, size_t width) { sh.kernel = libxsmm_create_packed_spgemm_csc(shape, flags, prefetch, (libxsmm_blasint)width, column_ptr, row_idx, values); return sh.kernel != nullptr; });
 }

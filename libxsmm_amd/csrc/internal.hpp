@@ -183,6 +183,7 @@ struct KernelCtx {
   // sparse creators
   int packed_width = 0, bk = 0, bn = 0;
   int sp_rows = 0, sp_inner = 0; unsigned int sp_nnz = 0;
+  size_t sp_nvals = 0;              // elements of the run-time values array the pattern reads (nnz; with a value map: its largest entry + 1)
   unsigned int* d_ptr = nullptr; unsigned int* d_idx = nullptr; void* d_vals = nullptr;  // device pattern (+ baked values)
   unsigned int* d_vmap = nullptr;   // value position per pattern entry (B-sparse CSR regrouped by column)
   int sp_ncols = 0, sp_skip_empty = 0;

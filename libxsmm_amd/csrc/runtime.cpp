@@ -996,7 +996,7 @@ void run_spmm(KernelCtx* k, const void* param, const BatchSpec& b) {
   if (!vals || !x || !y) { set_error(-2, "sparse kernel called with a NULL operand"); return; }
   {   // synchronous single calls accept plain host memory (e.g. values straight out of an .mtx reader's malloc)
     const size_t es = (a.dtype == LIBXSMM_DATATYPE_F64) ? 8 : 4;
-    if (!k->d_vals || !asp) vals = host_input(vals, es * (size_t)a.nnz, b.count);
+    if (!k->d_vals || !asp) vals = host_input(vals, es * k->sp_nvals, b.count);
     if (staging_allowed(b.count)) {
       // the dense operand and C may be PANELS of wider host matrices (PyFR hands column blocks of B and C with ldb = ldc = the full width
       // [ref: samples/xgemm_sparse_Ainregs/pyfr_driver_asp_reg.c:379-393]): only the touched bytes of every row / slab move, never the gaps
@@ -1707,7 +1707,9 @@ static void drop_unregistered(KernelCtx* c) { std::lock_guard<std::mutex> guard(
 static bool upload_pattern(KernelCtx* c, int rows, int inner, const unsigned int* ptr, const unsigned int* idx, const unsigned int* vmap) {
   const unsigned int nnz = ptr[rows];
   for (unsigned int z = 0; z < nnz; ++z) if ((int)idx[z] >= inner) return false;
-  c->sp_rows = rows; c->sp_inner = inner; c->sp_nnz = nnz;
+  c->sp_rows = rows; c->sp_inner = inner; c->sp_nnz = nnz; c->sp_nvals = nnz;
+  // a value map may reach past nnz: the row-major operand of _ac_rm / _bc_rm is read at k * ldb + n / m * lda + k
+  if (vmap) { c->sp_nvals = 0; for (unsigned int z = 0; z < nnz; ++z) c->sp_nvals = std::max<size_t>(c->sp_nvals, (size_t)vmap[z] + 1); }
   c->kname_single = c->kname_batched = "spmm_stream_kernel";
   c->d_ptr = to_device(ptr, (size_t)rows + 1); c->d_idx = to_device(idx, nnz);
   if (vmap) c->d_vmap = to_device(vmap, nnz);

@@ -73,3 +73,87 @@ def read_mtx(path):
         parts = ln.split()
         dense[int(parts[0]) - 1, int(parts[1]) - 1] = float(parts[2]) if len(parts) > 2 else 1.0
     return dense
+
+
+# ---- padded leading dimensions: poisoned gaps and a float64 restatement -------------------------------------------------------------------------
+# Dense operands are built with their leading axis widened to ld.  Input gaps hold NaN, so a kernel that reads one shows NaN in its output; C gaps
+# hold C_GAP, a finite pattern that must come back bit for bit.
+C_GAP = -7.0
+
+
+def gapped(x, ld, axis, fill):
+    """x with `axis` widened to ld; the added elements hold `fill`."""
+    shape = list(x.shape)
+    shape[axis] = ld
+    buf = np.full(shape, fill, dtype=x.dtype)
+    buf[logical_slice(x.ndim, axis, x.shape[axis])] = x
+    return buf
+
+
+def logical_slice(ndim, axis, width):
+    sl = [slice(None)] * ndim
+    sl[axis] = slice(0, width)
+    return tuple(sl)
+
+
+def gap_slice(ndim, axis, width):
+    sl = [slice(None)] * ndim
+    sl[axis] = slice(width, None)
+    return tuple(sl)
+
+
+def assert_gaps_untouched(got, width, axis, fill=C_GAP):
+    """The elements between the logical width and the leading dimension are bit-identical to `fill`."""
+    gap = got[gap_slice(got.ndim, axis, width)]
+    want = np.full(gap.shape, fill, dtype=got.dtype)
+    assert np.array_equal(gap.view(np.uint8), want.view(np.uint8)), f"{np.count_nonzero(gap != want)} gap elements of C were written"
+
+
+def dense_of_csr(rowptr, colidx, vals, rows, cols):
+    """float64 rows x cols matrix of a CSR pattern (no duplicate entries)."""
+    a = np.zeros((rows, cols))
+    a[np.repeat(np.arange(rows), np.diff(rowptr)), colidx] = np.asarray(vals, dtype=np.float64)
+    return a
+
+
+def assert_componentwise(got, ref, mag, terms, dt_np, untouched=None, c0=None):
+    """|got - ref| <= (terms + 2) * u * mag elementwise, u the unit round-off of dt_np; mag = sum |a| |x| (+ |C0| when beta = 1).
+    `untouched`: boolean mask (broadcast against got) of elements that must be bit-identical to c0."""
+    u = np.finfo(dt_np).eps / 2
+    g = got.astype(np.float64)
+    assert np.all(np.isfinite(g)), f"{np.count_nonzero(~np.isfinite(g))} non-finite results (a gap was read?)"
+    bound = (np.asarray(terms, dtype=np.float64) + 2) * u * mag
+    err = np.abs(g - ref)
+    bad = err > bound
+    assert not bad.any(), f"{np.count_nonzero(bad)} elements outside the componentwise bound; worst excess {float(np.max(err - bound)):.3e}"
+    if untouched is not None:
+        mask = np.broadcast_to(untouched, got.shape)
+        assert np.array_equal(got[mask].view(np.uint8), c0[mask].view(np.uint8)), "rows the operation leaves untouched were written"
+
+
+def ref_asparse(rowptr, colidx, vals, B, C0, beta0, skip_empty=True):
+    """A sparse (M x K, CSR) times packed B [K][N][P] -> C [M][N][P] in float64: (ref, mag, terms, untouched rows).
+    Empty rows are left untouched when skip_empty (packed CSR) or beta = 1 (every form)."""
+    M, (K, N, P) = len(rowptr) - 1, B.shape
+    A = dense_of_csr(rowptr, colidx, vals, M, K)
+    B64 = B.astype(np.float64).reshape(K, N * P)
+    ref, mag = (A @ B64).reshape(M, N, P), (np.abs(A) @ np.abs(B64)).reshape(M, N, P)
+    if not beta0:
+        ref, mag = ref + C0, mag + np.abs(C0.astype(np.float64))
+    nnz = np.diff(rowptr).astype(np.int64)
+    untouched = (nnz == 0) & (bool(skip_empty) or not beta0)
+    ref[untouched], mag[untouched] = C0[untouched], 0
+    return ref, mag, nnz[:, None, None], untouched[:, None, None]
+
+
+def ref_bsparse(Bs, A, C0, beta0):
+    """packed A [M][K][P] times dense-ified sparse B (K x N, float64) -> C [M][N][P]: (ref, mag, terms, untouched columns).
+    An empty column n is written as zeros with beta = 0 and left untouched with beta = 1."""
+    A64 = A.astype(np.float64)
+    ref, mag = np.einsum("mkp,kn->mnp", A64, Bs), np.einsum("mkp,kn->mnp", np.abs(A64), np.abs(Bs))
+    if not beta0:
+        ref, mag = ref + C0, mag + np.abs(C0.astype(np.float64))
+    nnz = np.count_nonzero(Bs, axis=0)
+    untouched = (nnz == 0) & (not beta0)
+    ref[:, untouched], mag[:, untouched] = C0[:, untouched], 0
+    return ref, mag, nnz[None, :, None], untouched[None, :, None]

@@ -241,6 +241,48 @@ def test_created_packed_kernels_sharded_over_the_packed_width(kind, shards, pitc
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["csr", "csc"])
+@pytest.mark.parametrize("pad", ["ldc", "dense"])
+def test_created_packed_kernels_sharded_refuse_padded_leading_dimensions(kind, pad):
+    """Every shard kernel writes C as [M][ldc][P_s], the gather moves M * N rows of P_s: only the compact per-shard layout the header documents is
+    accepted -- ldc = n + 3, or a padded dense operand (CSR, A sparse: ldb = n + 1; CSC, B sparse: lda = k + 1), gives NULL.  The natural leading
+    dimensions of the same problem (and of the B-sparse form of the CSR creator) still create a set."""
+    from sparse_helpers import random_csr, csr_to_csc
+    api = capi.load()
+    M, K, N, P, shards = (35, 35, 9, 1000, 3) if kind == "csr" else (9, 35, 35, 1000, 3)
+    rng = np.random.default_rng(7)
+    if kind == "csr":
+        ptr, idx = random_csr(rng, M, K, 0.15)
+        natural, (lda, ldb, ldc) = (0, N, N), (0, N + (pad == "dense"), N + 3 * (pad == "ldc"))
+    else:
+        rp, ci = random_csr(rng, K, N, 0.15)
+        ptr, idx, _ = csr_to_csc(rp, ci, np.arange(len(ci), dtype=np.float32), K, N)
+        natural, (lda, ldb, ldc) = (K, 0, N), (K + (pad == "dense"), 0, N + 3 * (pad == "ldc"))
+    ptr = np.ascontiguousarray(ptr, dtype=np.uint32); idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    vals = rng.standard_normal(len(idx)).astype(np.float32)
+    make = api.hip_create_packed_spgemm_csr_sharded if kind == "csr" else api.hip_create_packed_spgemm_csc_sharded
+    devices = (C.c_int * shards)(*[s % api.hip_device_count() for s in range(shards)])
+    # the plain creator takes the padded shape (tests/test_sparse_ld_gpu.py runs it) ...
+    create = api.create_packed_spgemm_csr if kind == "csr" else api.create_packed_spgemm_csc
+    h = create(capi.gemm_shape(M, N, K, lda, ldb, ldc, DT.F32, DT.F32, DT.F32, DT.F32), F.BETA_0, 0, P, ptr.ctypes.data, idx.ctypes.data, vals.ctypes.data)
+    assert h
+    api.release_kernel(h)
+    # ... the sharded one does not
+    assert not make(capi.gemm_shape(M, N, K, lda, ldb, ldc, DT.F32, DT.F32, DT.F32, DT.F32), F.BETA_0, 0, P, ptr.ctypes.data, idx.ctypes.data, vals.ctypes.data, shards, devices)
+    set_ = make(capi.gemm_shape(M, N, K, *natural, DT.F32, DT.F32, DT.F32, DT.F32), F.BETA_0, 0, P, ptr.ctypes.data, idx.ctypes.data, vals.ctypes.data, shards, devices)
+    assert set_ and api.hip_sharded_count(set_) == shards
+    api.hip_sharded_destroy(set_)
+    if kind == "csr":                      # the creator's B-sparse form (ldb = 0) in its compact layout stays shardable; padded, it is refused
+        rp, ci = random_csr(rng, K, N, 0.15)
+        bv = rng.standard_normal(len(ci)).astype(np.float32)
+        ok = make(capi.gemm_shape(M, N, K, K, 0, N, DT.F32, DT.F32, DT.F32, DT.F32), F.BETA_0, 0, P, rp.ctypes.data, ci.ctypes.data, bv.ctypes.data, shards, devices)
+        assert ok
+        api.hip_sharded_destroy(ok)
+        assert not make(capi.gemm_shape(M, N, K, K + 1, 0, N + 3 * (pad == "ldc"), DT.F32, DT.F32, DT.F32, DT.F32), F.BETA_0, 0, P,
+                        rp.ctypes.data, ci.ctypes.data, bv.ctypes.data, shards, devices)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("shards", [1, 2, 5])
 def test_created_bcsc_kernel_sharded_over_the_m_blocks(shards):
     """libxsmm_hip_create_packed_spgemm_bcsc_sharded: config #4's kernel, the M-blocks cut into contiguous ranges, the block-sparse B replicated per device"""
