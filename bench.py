@@ -5,9 +5,12 @@ Headline (the `value`): BASELINE.json configs[1] -- strided BRGEMM, fp32, m=n=k=
 (A_i, B_i, C_i) problems launched through ONE libxsmm_dispatch_brgemm(STRIDE) handle with
 libxsmm_hip_gemm_batch_strided.  One "step" = one such launch over one batch.
 
-Output contract: the LAST stdout line is one compact JSON object (< 3.5 KB: the driver keeps an 8 KB tail) with the headline, its roofline,
-the CPU baseline and one or two numbers per secondary workload; the full record of the run (every kernel name, time, verification norm,
-CPU sample description) goes to bench_detail.json next to this file and to stderr BEFORE that line.
+A plain run measures the headline and nothing else: set-up, --warmup launches, the --steps timed launches, --dump-outputs if given, the line.
+`--full` adds everything else below the roofline (every item from `verified` on), each after the headline's timed region.
+
+Output contract: the LAST stdout line is one compact JSON object (< 3.5 KB: the driver keeps an 8 KB tail) with the headline, its roofline
+and (--full) the CPU baseline and one or two numbers per secondary workload; the full record of the run (every kernel name, time, verification
+norm, CPU sample description) goes to bench_detail.json next to this file and to stderr BEFORE that line.
 
 What the record carries (all measured in this process, on this GPU):
   * value / ms_per_step: the timed region is exactly --steps back-to-back launches issued from hipGraphs (`steps_timed` = `steps`);
@@ -18,7 +21,8 @@ What the record carries (all measured in this process, on this GPU):
     depend on the arguments only, so two builds of the project can be compared output for output.
   * roofline: algorithmic bytes (br*(m*k*sA + k*n*sB) + m*n*sC*(1+[beta=1]) per problem) / HIP-event time per launch.
     `traffic` = TCC-counter bytes per launch from the committed PMC pass of this same command (profiles/), null if none.
-  * verified: after the timed region a strided sample of C is compared with the oracle (oracle/liboracle.so) on the same inputs.
+  * verified (--full; null otherwise): after the timed region a strided sample of C is compared with the oracle (oracle/liboracle.so) on the same inputs.
+  * without_streaming_hint / l3_resident (--full): the headline's launch without its streaming declaration, and on one Infinity-Cache-resident input set.
   * sweep: m in {16,32,64} x {f32,bf16}, streaming regime, at batch 4096 and 65536: GFLOP/s, frac of HBM roofline, % of MFMA peak.
   * reuse: the operand-reuse regimes -- B shared by the whole batch (stride_b = 0) and a blocked GEMM built from BRGEMM tiles
     (2-D batch, chain br = K/m, operands cache-resident): the only regime in which a percentage of MFMA peak is the binding roofline.
@@ -38,7 +42,8 @@ LOCAL_RANK) -- or, when the plain command `python bench.py --gpus N ...` is run 
 `--gpus N` means N ranks either way.  BENCH_DRY=1 is the plumbing check of exactly that on a box without GPUs (gloo, no kernel is
 launched, `value` 0, "dry": true): tests/test_bench_contract_cpu.py.
 `--config 5`: BASELINE configs[4] instead -- 2^20 bf16 64^3 problems with fused column-bias + ReLU, split over the ranks with
-libxsmm_hip_shard_range (strong scaling), compute leg and (with --gather) the result gather to rank 0 timed separately.
+libxsmm_hip_shard_range (strong scaling), compute leg and (with --gather) the result gather to rank 0 timed separately; --full adds the
+oracle check and the CPU baseline.
 """
 import argparse
 import ctypes as C
@@ -79,8 +84,9 @@ def parse():
     ap.add_argument("--min-seconds", type=float, default=0.5, help="minimum length of a secondary leg's timed region")
     ap.add_argument("--total", type=int, default=1 << 20, help="--config 5: problems over all ranks")
     ap.add_argument("--gather", action="store_true", help="--config 5: also time the gather of C to rank 0 (RCCL)")
-    ap.add_argument("--no-sweep", action="store_true", help="headline only (profiling passes)")
-    ap.add_argument("--no-l3", action="store_true", help="skip the Infinity-Cache-resident secondary leg")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the oracle check, the secondary legs, sweeps, configs and CPU baselines")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: no sweep / reuse / configs / tpp / pipelined groups (profiling passes)")
+    ap.add_argument("--no-l3", action="store_true", help="--full: skip the Infinity-Cache-resident and undeclared-streaming secondary legs")
     ap.add_argument("--eager", action="store_true", help="plain launches instead of hipGraph replays in the timed regions (counter-collection passes)")
     ap.add_argument("--manifest", default="", help="write the execution order of the launches (label, kernel, counts) to this JSON file")
     ap.add_argument("--only", default="", help="measure only this sweep/reuse entry (profiling passes), e.g. reuse:f32_m32_blocked")
@@ -957,7 +963,7 @@ def run_config5(args, api, dev, rank, world, dist, barrier):
     api.check()
     if args.dump_outputs and rank == 0:
         dump_outputs(work, args.steps, args.dump_outputs)
-    ok, err, cnt = work.verify(0)
+    ok, err, cnt = work.verify(0) if args.full else (None, 0.0, 0)
     gather_ms = None
     if args.gather and dist is not None:
         # the only collective of the path: the final result gather (RCCL over xGMI), timed on its own
@@ -974,14 +980,15 @@ def run_config5(args, api, dev, rank, world, dist, barrier):
         torch.cuda.synchronize(); barrier()
         gather_ms = (time.perf_counter() - t0) * 1e3
         if rank == 0:                                                   # the assembled result carries this rank's shard where shard_range says it lies
-            ok = ok and full_c is not None and full_c.shape[0] == args.total and bool(torch.equal(full_c[b.value:e.value], shard))
+            ok = ok is not False and full_c is not None and full_c.shape[0] == args.total and bool(torch.equal(full_c[b.value:e.value], shard))
     if dist is not None:
-        t = torch.tensor([elapsed, float(n), 0.0 if ok else 1.0], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed, float(n), 0.0 if ok is not False else 1.0], dtype=torch.float64, device=dev)
         tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed, bad = float(tmax[0].item()), float(tmax[2].item())
         tmin = t.clone(); dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         n = int(tmin[1].item())            # every rank times the same number of launches unless its estimate differed: count the fewest
-        ok = bad == 0.0
+        if ok is not None:                 # None: nothing was checked (a plain run without --gather)
+            ok = bad == 0.0
     if rank != 0:
         return None
     flops = 2.0 * 64 ** 3 * args.total * n
@@ -993,7 +1000,7 @@ def run_config5(args, api, dev, rank, world, dist, barrier):
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
            "config": {"workload": f"stride-BRGEMM bf16 m=n=k=64 br=1 beta=0 + column bias + ReLU, {args.total} problems split over {world} rank(s) by libxsmm_hip_shard_range",
                       "kernel": work.kernel(), "problems_per_gpu_rank0": mine, "parallelism": f"batch-split x{world}, no data-path collective"},
-           "rccl_ranks": world if dist is not None else 0, "verified": bool(ok), "verify_normf_rel": float(f"{err:.3g}"),
+           "rccl_ranks": world if dist is not None else 0, "verified": None if ok is None else bool(ok), "verify_normf_rel": float(f"{err:.3g}") if cnt else None,
            "pct_mfma_peak": round(100.0 * value / world / 1e3 / MFMA_PEAK_TF["bf16"], 2),
            "roofline": {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
                         "kernel_us": round(us, 3), "algorithmic_bytes_per_launch": int(per_gpu_bytes), "note": "rank 0's launch; every rank runs the same shard size +-1"}}
@@ -1052,7 +1059,7 @@ def main():
 
     if args.config == 5:
         out = run_config5(args, api, dev, rank, world, dist, barrier)
-        if rank == 0 and not args.no_cpu_baseline and world == 1:
+        if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(64, "bf16", 1, 0, 1, args.cpu_seconds, nthreads)
         finish(dist, out if rank == 0 else None, args.detail)
         return
@@ -1096,16 +1103,18 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(work, args.steps, args.dump_outputs)
     headline_kernel, headline_hint = work.kernel(), work.hint
-    verified, verr, vcnt = (work.verify(0) if args.beta == 0 else (None, 0.0, 0))
+    verified, verr, vcnt = (work.verify(0) if args.full and args.beta == 0 else (None, 0.0, 0))
     if dist is not None:
         t = torch.tensor([elapsed, -float(n_timed), 0.0 if verified in (True, None) else 1.0], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, n_timed = float(t[0].item()), int(-t[1].item())
         if verified is not None:
             verified = t[2].item() == 0.0
+    # --full: everything below is measured after the headline and takes no part in it
+    extra = args.full and rank == 0 and world == 1
     # secondary measurement: the same set every step (Infinity-Cache resident), not the headline
     l3_us = auto_us = None
-    if not args.no_l3:
+    if args.full and not args.no_l3:
         # the same rotation without the declaration (hint 0: the library decides by launch size and, since round 6, by the thread's recent operand sets together)
         work.hint = 0
         _, _, auto_us = timed(work, args.steps, min(args.min_seconds, 0.2), label=work.label() + "_hint0")
@@ -1114,7 +1123,7 @@ def main():
         del l3
 
     sweep, reuse, ragged = {}, {}, {}
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if extra and not args.no_sweep:
         quick = min(args.min_seconds, 0.15)
         for dt, m, b in RAGGED:
             w = Workload(api, dev, dt, m, b)
@@ -1135,19 +1144,19 @@ def main():
             reuse[w.label()] = r
             del w; torch.cuda.empty_cache()
     configs, roof = {}, None
-    if rank == 0 and world == 1 and not args.no_sweep and not args.no_configs:
+    if extra and not args.no_sweep and not args.no_configs:
         configs = run_configs(api, dev, args.steps, min(args.min_seconds, 0.15), args.cpu_seconds, not args.no_cpu_baseline)
     round4 = {}
-    if rank == 0 and world == 1 and not args.no_sweep and not args.no_configs:
+    if extra and not args.no_sweep and not args.no_configs:
         round4 = run_round4(api, dev, args.steps, min(args.min_seconds, 0.15))
     tpp = {}
-    if rank == 0 and world == 1 and not args.no_sweep and not args.no_configs:
+    if extra and not args.no_sweep and not args.no_configs:
         # SURVEY 8 rows a11 / f1 / f2 in the driver-visible line (round-4 review item 4): tools/tpp_group.py -- measured like the headline, verified against the oracle
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import tpp_group
         tpp = tpp_group.run(api, dev, args.steps, min(args.min_seconds, 0.15), args.cpu_seconds, not args.no_cpu_baseline, timed)
     pipelined = None
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if extra and not args.no_sweep:
         pipelined = run_pipelined(api, dev, args.steps, min(args.min_seconds, 0.15), lanes=int(os.environ.get("BENCH_LANES", "8")))
         roof = mfma_roof(api, dev)
         for r in reuse.values():           # blocked entries next to what the pipe sustains on this data, on this chip, today
@@ -1230,7 +1239,7 @@ def main():
                 out["profiles_check"] = chk
                 for msg in chk["stale"]:
                     print(f"bench.py: WARNING: {chk['table']} does not reproduce this run -- {msg} (re-run tools/profile_paths.sh)", file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.m, args.dtype, args.br, args.beta, args.fused, args.cpu_seconds, nthreads)
             if sweep:
                 out["single_call_us"] = single_call_latency()

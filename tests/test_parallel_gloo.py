@@ -264,7 +264,7 @@ def test_bench_config5_two_ranks_end_to_end_on_one_device():
     env = dict(os.environ, BENCH_BACKEND="gloo", BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "5", "--gather", "--total", "8192", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05",
-           "--no-cpu-baseline", "--detail", ""]
+           "--full", "--no-cpu-baseline", "--detail", ""]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -286,7 +286,7 @@ def test_bench_plain_command_spawns_two_ranks_on_one_device():
     env = dict(os.environ, BENCH_BACKEND="gloo", BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--min-seconds", "0.05", "--no-sweep", "--no-l3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--min-seconds", "0.05", "--full", "--no-sweep", "--no-l3",
            "--no-cpu-baseline", "--detail", ""]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

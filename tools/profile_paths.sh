@@ -15,7 +15,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5"
+B="python $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 5"
 if [ "$WHAT" = all ] || [ "$WHAT" = trace ]; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_trace -- $B --min-seconds 0.05 --manifest $OUT/bench_trace_manifest.json > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 fi
