@@ -151,6 +151,31 @@ LIBXSMM_API void libxsmm_hip_meltw_ternary_batch_strided(libxsmm_meltwfunction_t
 LIBXSMM_API void libxsmm_hip_meqn_batch_strided(libxsmm_meqn_function kernel, const libxsmm_meqn_param* param, size_t count,
   int ninputs, const long long* stride_inputs, long long stride_output, long long stride_output_aux,
   int nops_args, const long long* stride_ops_args);
+/**
+ * Grouped batch: several strided batches, each through its own (BR)GEMM handle and so of its own shape, in one call -- the caller that calls several
+ * handles from its OpenMP region [ref: samples/xgemm/gemm_kernel.c:4063-4066]:
+ *   libxsmm_hip_gemm_batch_grouped(groups, ngroups)
+ *     ==  for (g = 0; g < ngroups; ++g)
+ *           libxsmm_hip_gemm_batch_strided(groups[g].kernel, &groups[g].param, groups[g].count, groups[g].stride_a, groups[g].stride_b, groups[g].stride_c);
+ * The caller declares that no group reads or writes what another group writes (the contract of a pipeline section); the elements of one group follow
+ * libxsmm_hip_gemm_batch_strided.  Groups through plain or STRIDE batch-reduce handles of f32 x f32 -> f32 or bf16 x bf16 -> f32 / bf16 (A flat or VNNI_A,
+ * B flat, C not VNNI, no transposes) leave as ONE launch per precision class, except f32 groups of 2048 work items (element x C tile) or more, which are
+ * faster on their own kernels; a class with a single such group, and every other accepted handle (other types, transposes, ADDRESS /
+ * OFFSET batch-reduce, bitmask-compressed A, packed sparse), runs as that group's own strided launch, in list order, on the same stream.  Follows the
+ * thread's launch mode: blocking (returns when every group is done), stream-ordered (valid after libxsmm_hip_sync), coalescing (the queue is flushed
+ * first), inside a pipeline section (the launches go to the section's lanes).  Operands must be device-accessible -- for groups of count 1 as well, where a
+ * blocking libxsmm_hip_gemm_batch_strided call would still stage host-resident operands: the grouped launch reads them on the device as they are.  Every group is
+ * validated before anything is launched.  Error -2: groups == NULL with ngroups > 0, a batch-reduce handle without op.tertiary; -3: an unknown, TPP /
+ * equation or ext handle, or a call while the thread's stream is being captured into a graph (the group table lives for the call only).  count = 0 skips
+ * a group.
+ */
+typedef struct libxsmm_hip_gemm_group {
+  libxsmm_gemmfunction kernel;      /* any handle libxsmm_hip_gemm_batch_strided accepts (no ext handles) */
+  libxsmm_gemm_param   param;       /* element 0 of the group; op.tertiary = batch-reduce count for BRGEMM handles */
+  size_t               count;       /* elements of this group; 0 = skipped */
+  long long            stride_a, stride_b, stride_c;   /* byte strides of the primary slots; 0 = shared (weights) */
+} libxsmm_hip_gemm_group;
+LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* groups, size_t ngroups);
 
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns

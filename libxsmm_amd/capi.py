@@ -163,6 +163,11 @@ class HipShard(C.Structure):           # libxsmm_hip_shard (include/libxsmm_hip.
                 ("gather_rows", C.c_size_t), ("gather_src_pitch", C.c_size_t), ("gather_dst_pitch", C.c_size_t)]
 
 
+class GemmGroup(C.Structure):          # libxsmm_hip_gemm_group (include/libxsmm_hip.h): one strided batch of a grouped call
+    _fields_ = [("kernel", C.c_void_p), ("param", GemmParam), ("count", C.c_size_t),
+                ("stride_a", C.c_longlong), ("stride_b", C.c_longlong), ("stride_c", C.c_longlong)]
+
+
 class KernelInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("nflops", C.c_uint), ("code_size", C.c_size_t), ("is_reference_kernel", C.c_uint)]
 
@@ -279,6 +284,7 @@ class Api:
             self.hip_gemm_batch_strided_2d = f("hip_gemm_batch_strided_2d", None, [vp, C.POINTER(GemmParam), C.c_size_t, C.c_size_t, ll, ll, ll, ll])
             self.hip_gemm_ext_batch_strided_2d = f("hip_gemm_ext_batch_strided_2d", None, [vp, C.POINTER(GemmExtParam), C.c_size_t, C.c_size_t, ll, ll, ll, ll, ll, ll, ll])
             self.hip_gemm_batch_pointers = f("hip_gemm_batch_pointers", None, [vp, C.POINTER(GemmParam), C.c_size_t, vp, vp, vp])
+            self.hip_gemm_batch_grouped = f("hip_gemm_batch_grouped", None, [C.POINTER(GemmGroup), C.c_size_t])
             self.hip_meltw_unary_batch_strided = f("hip_meltw_unary_batch_strided", None, [vp, C.POINTER(UnaryParam), C.c_size_t, ll, ll, ll])
             self.hip_meltw_binary_batch_strided = f("hip_meltw_binary_batch_strided", None, [vp, C.POINTER(BinaryParam), C.c_size_t, ll, ll, ll])
             self.hip_meltw_ternary_batch_strided = f("hip_meltw_ternary_batch_strided", None, [vp, C.POINTER(TernaryParam), C.c_size_t, ll, ll, ll, ll])

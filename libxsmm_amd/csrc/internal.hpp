@@ -107,6 +107,21 @@ struct MeltwArgs {
   int nt;                                             // round 6: the launch's operands cannot be cache resident (footprint, streaming hint): non-temporal loads and stores in the streaming kernels
 };
 
+// libxsmm_hip_gemm_batch_grouped: one eligible group as the grouped kernels read it (gemm_grouped_kernels.hip); a table of these is uploaded per call
+struct GemmGroupDesc {
+  const char* a; const char* b; char* c;            // `primary` slots of the group's element 0
+  long long sa, sb, sc;                             // element byte strides (0: shared)
+  long long br_sa, br_sb;                           // STRIDE batch-reduce byte strides
+  unsigned long long first;                         // exclusive prefix of work items over the table (item = element x C tile)
+  unsigned long long br_count;                      // 1 for plain GEMM handles
+  int m, n, k, lda, ldb, ldc;
+  int tiles_m, tiles_n, tile;                       // C tiles of one element, tile edge 16 or 32
+  int beta1, vnni_a, c_bf16;                        // beta = 1, bf16 A in VNNI-2 layout, bf16 C (else f32)
+  int a_vec4;                                       // bf16: VNNI A pairs 4-byte aligned (every element, every block)
+  int b_vec16, b_vec8;                              // B columns 16- / 8-byte aligned (every element, every block)
+};
+static_assert(sizeof(GemmGroupDesc) == 144, "the grouped kernels' table entry");
+
 // sparse operator S (rows x inner) applied to a packed panel:
 //   Y[r][q] (+)= sum_z val[z] * X[idx[z]][q],   q = 0..ncols-1 contiguous, for `nouter` slabs
 struct SpmmArgs {
@@ -271,6 +286,10 @@ bool meltw_supported(const libxsmm_meltw_descriptor& d);
 int launch_mfma_probe(int bf16, const void* operands, int iterations, void* stream, double* flop);
 int launch_brchain_f32(const GemmArgs& args, float* partial, size_t partial_capacity_tiles, int* nslices, void* stream, const char** kernel_name);
 int launch_brsplit_reduce(const GemmArgs& args, const float* partial, int nsplit, void* stream);
+int launch_gemm_grouped(const GemmGroupDesc* table, int ngroups, unsigned long long items, int bf16, void* stream);   // table: device copy, groups ordered by `first`
+constexpr int kGroupedInline = 24;                // tables of up to this many groups travel in the kernel arguments (launch_gemm_grouped_inline: host table)
+int launch_gemm_grouped_inline(const GemmGroupDesc* host_table, int ngroups, unsigned long long items, int bf16, void* stream);
+const char* gemm_grouped_kernel_name(int bf16);
 int launch_spmm(const SpmmArgs& args, void* stream, const char** kernel_name);
 int launch_bcsc(const BcscArgs& args, void* stream, const char** kernel_name);
 // Automatic streaming decision (libxsmm_hip_set_streaming_hint(0)): a launch whose own operands exceed the Infinity Cache streams -- and so does a launch whose operands

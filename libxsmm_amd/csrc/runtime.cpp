@@ -11,6 +11,7 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <cstdarg>
@@ -2209,6 +2210,109 @@ LIBXSMM_API void libxsmm_hip_meqn_batch_strided(libxsmm_meqn_function kernel, co
   if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
   scratch_reset();
   if (const char* kname = run_meqn_batch(c->eqn, param, b)) c->kname_batched = kname;
+}
+// ---- grouped batches (libxsmm_hip_gemm_batch_grouped): several shapes, one launch per precision class --------------------------------------------------
+// A group enters the grouped kernels (gemm_grouped_kernels.hip) when its handle is a plain GEMM or a STRIDE batch-reduce handle of f32 x f32 -> f32 or
+// bf16 x bf16 -> f32 / bf16 (A flat or VNNI-2, B flat, C not VNNI), NN, with no flag beyond beta and the hints; `cls` = 0 (f32) or 1 (bf16).
+static constexpr unsigned long long kGroupedOwnF32Items = 2048;
+static bool grouped_eligible(const KernelCtx* k, const libxsmm_hip_gemm_group& grp, GemmGroupDesc& g, int& cls) {
+  if (k->kind != K_GEMM) return false;
+  const libxsmm_gemm_descriptor& d = k->g;
+  const unsigned int f = effective_gemm_flags(d);
+  const unsigned int allowed = LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_ALIGN_A | LIBXSMM_GEMM_FLAG_ALIGN_C_NTS_HINT | LIBXSMM_GEMM_FLAG_NO_RESET_TILECONFIG |
+    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE;
+  if (f & ~allowed) return false;
+  const bool f32 = d.a_type == LIBXSMM_DATATYPE_F32 && d.b_type == LIBXSMM_DATATYPE_F32 && d.c_type == LIBXSMM_DATATYPE_F32;
+  const bool bf16 = d.a_type == LIBXSMM_DATATYPE_BF16 && d.b_type == LIBXSMM_DATATYPE_BF16 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF16);
+  if (!f32 && !bf16) return false;
+  const libxsmm_gemm_param& p = grp.param;
+  if (d.m == 0 || d.n == 0 || d.k == 0 || !p.a.primary || !p.b.primary || !p.c.primary) return false;
+  unsigned long long brc = 1;
+  if (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) { brc = *(const unsigned long long*)p.op.tertiary; if (brc == 0) return false; }
+  // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers)
+  const unsigned long long lim = 1ull << 31;
+  if ((unsigned long long)d.lda * (d.k + 1) >= lim || (unsigned long long)d.ldb * d.n >= lim || (unsigned long long)d.ldc * d.n >= lim) return false;
+  const int tile = (d.m <= 16 && d.n <= 16) ? 16 : 32;
+  const unsigned long long tiles = (unsigned long long)((d.m + tile - 1) / tile) * ((d.n + tile - 1) / tile);
+  if (grp.count * tiles >= (1ull << 32)) return false;             // the kernels decode a group's items with 32-bit divisions
+  std::memset(&g, 0, sizeof(g));
+  g.a = (const char*)p.a.primary; g.b = (const char*)p.b.primary; g.c = (char*)p.c.primary;
+  g.sa = grp.stride_a; g.sb = grp.stride_b; g.sc = grp.stride_c;
+  g.br_sa = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_a : 0; g.br_sb = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_b : 0;
+  g.br_count = brc;
+  g.m = (int)d.m; g.n = (int)d.n; g.k = (int)d.k; g.lda = (int)d.lda; g.ldb = (int)d.ldb; g.ldc = (int)d.ldc;
+  g.tile = tile; g.tiles_m = (int)((d.m + tile - 1) / tile); g.tiles_n = (int)((d.n + tile - 1) / tile);
+  g.beta1 = (f & LIBXSMM_GEMM_FLAG_BETA_0) ? 0 : 1;
+  g.vnni_a = (bf16 && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
+  g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
+  const unsigned long long ua = (unsigned long long)(uintptr_t)g.a | (unsigned long long)g.sa | (unsigned long long)g.br_sa;
+  const unsigned long long ub = (unsigned long long)(uintptr_t)g.b | (unsigned long long)g.sb | (unsigned long long)g.br_sb | ((unsigned long long)d.ldb * (bf16 ? 2 : 4));
+  g.a_vec4 = (bf16 && (ua & 3) == 0) ? 1 : 0;
+  g.b_vec16 = (ub & 15) == 0 ? 1 : 0;
+  g.b_vec8 = (ub & 7) == 0 ? 1 : 0;
+  g.first = grp.count * tiles;                          // (the item count: turned into the exclusive prefix when the table is complete)
+  cls = bf16 ? 1 : 0;
+  return true;
+}
+LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* groups, size_t ngroups) {
+  if (ngroups == 0) return;
+  if (!groups) { set_error(-2, "libxsmm_hip_gemm_batch_grouped: groups is NULL but ngroups = %zu", ngroups); return; }
+  // every group is validated before anything is launched, with the codes libxsmm_hip_gemm_batch_strided sets
+  bool any = false;
+  for (size_t i = 0; i < ngroups; ++i) {
+    const libxsmm_hip_gemm_group& grp = groups[i];
+    KernelCtx* c = ctx_from_handle((const void*)grp.kernel);
+    if (!c) { set_error(-3, "libxsmm_hip_gemm_batch_grouped: group %zu has an unknown kernel handle", i); return; }
+    if (grp.count == 0) continue;
+    if (c->kind != K_GEMM && c->kind != K_SPMM_ASPARSE && c->kind != K_SPMM_BSPARSE) { set_error(-3, "libxsmm_hip_gemm_batch_grouped: group %zu: handle is not a (BR)GEMM or packed sparse kernel", i); return; }
+    if (c->kind == K_GEMM && (c->g.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI)) { set_error(-3, "libxsmm_hip_gemm_batch_grouped: group %zu: ext handles are not taken (use libxsmm_hip_gemm_ext_batch_strided)", i); return; }
+    if (c->kind == K_GEMM && (c->g.flags & (LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE)) && !grp.param.op.tertiary) {
+      set_error(-2, "libxsmm_hip_gemm_batch_grouped: group %zu: BRGEMM handle without op.tertiary (batch-reduce count)", i); return;
+    }
+    any = true;
+  }
+  if (!any) return;
+  {  // the group table is uploaded for this call only: a graph that replayed the launch would read whatever the staging slot holds by then
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (cur_stream() != nullptr && hipStreamIsCapturing(cur_stream(), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    if (cs != hipStreamCaptureStatusNone) { set_error(-3, "libxsmm_hip_gemm_batch_grouped cannot be captured into a graph (its group table lives for the call only): launch the groups one by one under capture"); return; }
+  }
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  std::vector<GemmGroupDesc> table[2];
+  std::vector<size_t> member[2], own;                   // own: groups that run as their own strided launch
+  for (size_t i = 0; i < ngroups; ++i) {
+    if (groups[i].count == 0) continue;
+    GemmGroupDesc gd; int cls = 0;
+    // measured: an f32 group of 2048 work items or more runs at least as fast on its own tuned kernel (p16s, lean, wg64, ragged families:
+    // 1.0 - 2x the grouped kernel's rate at 1024 - 4096 problems) as inside the grouped launch, so it leaves it (gd.first: the group's item count); bf16 groups
+    // gain from the merge and stay
+    if (grouped_eligible(ctx_from_handle((const void*)groups[i].kernel), groups[i], gd, cls) && !(cls == 0 && gd.first >= kGroupedOwnF32Items)) {
+      table[cls].push_back(gd); member[cls].push_back(i);
+    } else own.push_back(i);
+  }
+  for (int cls = 0; cls < 2; ++cls) {
+    if (table[cls].size() == 1) { own.push_back(member[cls][0]); continue; }     // a single shape keeps its own tuned kernel family
+    if (table[cls].empty()) continue;
+    unsigned long long items = 0;
+    for (GemmGroupDesc& gd : table[cls]) { const unsigned long long n = gd.first; gd.first = items; items += n; }
+    int err;
+    if (table[cls].size() <= (size_t)kGroupedInline) err = launch_gemm_grouped_inline(table[cls].data(), (int)table[cls].size(), items, cls, tls().stream);   // in the kernel arguments
+    else {
+      const GemmGroupDesc* dev = (const GemmGroupDesc*)stage_host(table[cls].data(), table[cls].size() * sizeof(GemmGroupDesc));
+      if (!dev) return;
+      err = launch_gemm_grouped(dev, (int)table[cls].size(), items, cls, tls().stream);
+    }
+    finish_launch(err, gemm_grouped_kernel_name(cls));
+  }
+  std::sort(own.begin(), own.end());
+  for (size_t i : own) {
+    const libxsmm_hip_gemm_group& grp = groups[i];
+    KernelCtx* c = ctx_from_handle((const void*)grp.kernel);
+    BatchSpec b; b.count = grp.count; b.s[0] = grp.stride_a; b.s[1] = grp.stride_b; b.s[2] = grp.stride_c;
+    if (c->kind == K_GEMM) run_gemm(c, &grp.param, b); else run_spmm(c, &grp.param, b);
+  }
 }
 // ---- multi-device launch from ONE host thread (the reference's scale-out axis is the caller's loop,
 // samples/xgemm/gemm_kernel.c:4063-4066) --------------------------------------------------------------------------------------------------------
