@@ -152,6 +152,34 @@ LIBXSMM_API void libxsmm_hip_meqn_batch_strided(libxsmm_meqn_function kernel, co
   int ninputs, const long long* stride_inputs, long long stride_output, long long stride_output_aux,
   int nops_args, const long long* stride_ops_args);
 /**
+ * Accumulating strided batch of a matrix equation: the caller's loop whose every iteration reads AND writes the same output -- the dgamma / dbeta sums
+ * of a layernorm backward pass [ref: samples/equation/equation_layernorm.c, tpp_layernorm_bwd_fp32: dgamma_func / dbeta_func inside the s2 loop]:
+ *   libxsmm_hip_meqn_batch_strided_accumulate(kernel, param, count, ninputs, stride_inputs, nops_args, stride_ops_args, order)
+ *     ==  for (i = 0; i < count; ++i) { q = *param;                      (in THIS order)
+ *           q.inputs[k].primary   = (char*)param->inputs[k].primary   + i * stride_inputs[k];
+ *           q.ops_args[k].primary = (char*)param->ops_args[k].primary + i * stride_ops_args[k];
+ *           kernel(&q); }                                                (q.output is NOT stepped)
+ * At least one input position of the tree must be the carried operand: inputs[k].primary == output.primary, stride_inputs[k] == 0, declared with the
+ * output's m, n, ld and type.  Element i reads it as element i - 1 left it.  No other operand may overlap the output.  F32 and BF16 outputs.
+ * order = LIBXSMM_HIP_MEQN_ORDER_LOOP: the result has the bits of the loop above -- every element's rounding in the loop's sequence (a BF16 output is
+ * rounded to BF16 after every element).  Element-wise trees run as ONE launch (the elements are walked inside the kernel); trees with reductions or
+ * GEMM nodes, misaligned operands and LIBXSMM_HIP_JIT=0 run the elements one after another through the single-call path.
+ * order = LIBXSMM_HIP_MEQN_ORDER_ANY: the caller allows the sum over the elements to be re-associated.  It is a permission, not a request: it takes effect
+ * for an F32 output whose head is output + x (BINARY_ADD, no broadcast) or output + x * y (TERNARY_MULADD, the output as in2) with the carried position
+ * nowhere else in the tree, and only for the sizes where it is faster.  Then the element axis is cut into S contiguous slices,
+ * S a function of (count, m, n) alone; slice s sums its elements [s * count / S, (s + 1) * count / S) in ascending order starting from +0, the S partial sums
+ * are added in ascending slice order, and the output's original value is added last.  No atomics: the same bits in every run, on every stream.
+ * Follows the thread's launch mode as libxsmm_hip_meqn_batch_strided does: blocking (per-element 1 x 1 inputs, e.g. arrays with stride 4, may be host
+ * memory), stream-ordered, or coalescing (the queue is flushed first).  Errors are set before anything is launched.  -3: not an equation handle; no
+ * carried operand; a carried operand whose shape, leading dimension or type differs from the output's; a head with a side channel (output.secondary:
+ * ReLU bitmask, UNZIP, SCATTER); a DUMP destination with stride 0 while count > 1; a non-zero stride on something shared (as the strided entry); an unknown
+ * order.  -2: fewer input strides than the equation's input positions.  count = 0 does nothing.  stride_ops_args may be NULL (all zero).
+ */
+#define LIBXSMM_HIP_MEQN_ORDER_LOOP 0   /* exactly the loop's sequence of roundings */
+#define LIBXSMM_HIP_MEQN_ORDER_ANY  1   /* the caller allows the sum over elements to be re-associated */
+LIBXSMM_API void libxsmm_hip_meqn_batch_strided_accumulate(libxsmm_meqn_function kernel, const libxsmm_meqn_param* param,
+  size_t count, int ninputs, const long long* stride_inputs, int nops_args, const long long* stride_ops_args, int order);
+/**
  * Grouped batch: several strided batches, each through its own (BR)GEMM handle and so of its own shape, in one call -- the caller that calls several
  * handles from its OpenMP region [ref: samples/xgemm/gemm_kernel.c:4063-4066]:
  *   libxsmm_hip_gemm_batch_grouped(groups, ngroups)

@@ -187,6 +187,8 @@ UNARY_FN = C.CFUNCTYPE(None, C.POINTER(UnaryParam))
 BINARY_FN = C.CFUNCTYPE(None, C.POINTER(BinaryParam))
 TERNARY_FN = C.CFUNCTYPE(None, C.POINTER(TernaryParam))
 MEQN_FN = C.CFUNCTYPE(None, C.POINTER(MeqnParam))
+# libxsmm_hip_meqn_batch_strided_accumulate: `order`
+MEQN_ORDER_LOOP, MEQN_ORDER_ANY = 0, 1
 
 # every symbol include/libxsmm.h and libxsmm_hip.h declare (checked by tests/test_capi_symbols.py)
 _DECL_RE = re.compile(r"LIBXSMM_API\s+[^;(]*?\b(libxsmm_\w+)\s*\(")
@@ -290,6 +292,7 @@ class Api:
             self.hip_meltw_ternary_batch_strided = f("hip_meltw_ternary_batch_strided", None, [vp, C.POINTER(TernaryParam), C.c_size_t, ll, ll, ll, ll])
             pll = C.POINTER(ll)
             self.hip_meqn_batch_strided = f("hip_meqn_batch_strided", None, [vp, C.POINTER(MeqnParam), C.c_size_t, C.c_int, pll, ll, ll, C.c_int, pll])
+            self.hip_meqn_batch_strided_accumulate = f("hip_meqn_batch_strided_accumulate", None, [vp, C.POINTER(MeqnParam), C.c_size_t, C.c_int, pll, C.c_int, pll, C.c_int])
             pu = C.POINTER(C.POINTER(C.c_uint))
             self.hip_mtx_read = f("hip_mtx_read", C.c_int, [C.c_char_p, C.c_int, C.c_int, pu, pu, C.POINTER(vp), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)])
             self.hip_bcsc_from_dense = f("hip_bcsc_from_dense", C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, pu, pu, C.POINTER(vp), C.POINTER(C.c_uint)])

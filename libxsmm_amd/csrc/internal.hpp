@@ -227,6 +227,10 @@ void run_meqn(EqnPlan* plan, const void* param);
 struct MeqnBatch { size_t count; int ninputs; const long long* s_in; long long s_out, s_aux; int nops; const long long* s_ops; };
 bool meqn_batch_prepare(EqnPlan* plan, const MeqnBatch& b);                  // validation + the batched kernel (no device needed); false: error set
 const char* run_meqn_batch(EqnPlan* plan, const void* param, const MeqnBatch& b);     // returns the name of the kernel that ran (nullptr: nothing ran)
+// libxsmm_hip_meqn_batch_strided_accumulate: as MeqnBatch, the output is not stepped; `order`: LIBXSMM_HIP_MEQN_ORDER_*
+struct MeqnAcc { size_t count; int ninputs; const long long* s_in; int nops; const long long* s_ops; int order; };
+bool meqn_acc_prepare(EqnPlan* plan, const void* param, const MeqnAcc& b, std::vector<int>& carried);   // validation + the carried / sliced kernels (no device needed)
+const char* run_meqn_acc(EqnPlan* plan, const void* param, const MeqnAcc& b, const std::vector<int>& carried);
 void free_meqn_plan(EqnPlan* plan);
 void free_meqn_equations();                      // libxsmm_finalize: drop every equation object
 const char* meqn_plan_name(const EqnPlan* plan);

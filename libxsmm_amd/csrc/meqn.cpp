@@ -61,6 +61,11 @@ struct EqnPlan {
   // libxsmm_hip_meqn_batch_strided: the batched form of `fused`, generated and compiled when the batched entry first meets the handle
   int eqn_idx = -1; libxsmm_meqn_arg_shape out_shape{};
   JitKernel* fused_b = nullptr; bool fused_b_tried = false; bool fused_b_phased = false; long long fused_b_total = 0;
+  // libxsmm_hip_meqn_batch_strided_accumulate: the carried (`_c`) and sliced (`_s` + combine) forms of `fused`, per set of carried input positions,
+  // generated when the accumulating entry first meets the handle with that set (nullptr: that form does not exist for this tree -> the element loop)
+  struct AccForms { JitKernel* carried = nullptr; JitKernel* sliced = nullptr; JitKernel* combine = nullptr; bool sliced_tried = false;
+    std::vector<int> c_inputs, s_inputs; std::vector<char> c_scalar, s_scalar; std::vector<int> c_types, s_types; };     // kernel-argument order of each form
+  std::map<std::vector<int>, AccForms> acc;
 };
 
 namespace {
@@ -289,6 +294,73 @@ bool scalar_reduce(const Equation& e, int id, int M, int N, ScalarReduce& r) {
   return e.nodes[r.src].m == M && e.nodes[r.src].n == N;
 }
 
+enum { FUSED_SINGLE = 0, FUSED_BATCHED = 1, FUSED_CARRIED = 2, FUSED_SLICED = 3 };
+constexpr int kAccAhead = 4;      // elements whose operand loads are issued before the first of them is used
+// The two generated forms of libxsmm_hip_meqn_batch_strided_accumulate for an element-wise tree.  A thread owns one 8-row unit of the output and walks the
+// elements itself, in ascending order, with `acc` (8 registers) as the value that goes from one element to the next; `loads` / `body` are one element's
+// operand loads and arithmetic from generate_fused's walk, with '@' in every per-element name.  The loads do not depend on `acc`, so the loop is unrolled
+// kAccAhead times with all loads of the kAccAhead elements in front of the first element's arithmetic: kAccAhead x (16 or 32 bytes per operand) in flight
+// per thread while the chain of dependent operations runs.
+//   carried (`_c`): acc starts as the output's current value, every element's head result becomes acc (a BF16 output: through the rounding st_bf16 /
+//     ld_bf16 apply between two calls of the caller's loop), and the output is stored once -- the loop's own sequence of operations, for any tree.
+//   sliced (`_s`):  grid.y walks `slices` contiguous slices of the element axis, slice sl = elements [sl * count / slices, (sl + 1) * count / slices)
+//     (integer division); acc starts as +0 and body adds g(element) to it; the partial goes to part[sl][j][i] (f32, N x M, ld = M).
+void emit_accumulating(bool carry, const std::string& fname, long long units, int M, int N, const libxsmm_meqn_arg_shape& out, size_t nin, size_t nalpha,
+                       const std::string& loads, const std::string& body, std::string& src) {
+  char buf[512];
+  const bool bf16 = out.type == LIBXSMM_DATATYPE_BF16;
+  src = kFusedPrelude;
+  src += "extern \"C\" __global__ __launch_bounds__(256) void " + fname + "(";
+  for (size_t k = 0; k < nin; ++k) src += "const void* in" + std::to_string(k) + "_, ";
+  src += carry ? "void* out_" : "void* part_";
+  for (size_t k = 0; k < nalpha; ++k) src += ", float alpha" + std::to_string(k);
+  for (size_t k = 0; k < nin; ++k) src += ", long long s_in" + std::to_string(k);
+  src += carry ? ", long long count) {\n" : ", long long count, long long slices) {\n";
+  std::snprintf(buf, sizeof(buf), "  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;\n  if (t >= %lldLL) return;\n  const long long j = t / %d, i = (t - j * %d) * 8;\n", units, M / 8, M / 8);
+  src += buf;
+  std::string step;                                   // the pointers of element el + @
+  for (size_t k = 0; k < nin; ++k) step += "  const void* in" + std::to_string(k) + "_@ = (const char*)in" + std::to_string(k) + "_ + (el + @) * s_in" + std::to_string(k) + ";\n";
+  const std::string keep = !carry ? "" : !bf16 ? "  _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) acc[e] = v0[e];\n"
+    : "  _Pragma(\"unroll\") for (int e = 0; e < 4; ++e) { const unsigned int pk = f2bf_pk(v0[2 * e], v0[2 * e + 1]); acc[2 * e] = __uint_as_float(pk << 16); acc[2 * e + 1] = __uint_as_float(pk & 0xffff0000u); }\n";
+  const auto at = [](std::string text, int u) { std::replace(text.begin(), text.end(), '@', (char)('0' + u)); return text; };
+  const auto loop = [&](const char* end) {
+    std::string l = std::string("  for (; el + ") + std::to_string(kAccAhead) + " <= " + end + "; el += " + std::to_string(kAccAhead) + ") {\n";
+    for (int u = 0; u < kAccAhead; ++u) l += at(step + loads, u);
+    for (int u = 0; u < kAccAhead; ++u) l += "  {\n" + at(body, u) + keep + "  }\n";
+    l += std::string("  }\n  for (; el < ") + end + "; ++el) {\n" + at(step + loads, 0) + "  {\n" + at(body, 0) + keep + "  }\n  }\n";
+    return l;
+  };
+  if (carry) {
+    src += std::string("  float acc[8]; ") + (bf16 ? "ld_bf16(acc, (GM const unsigned short*)" : "ld_f32(acc, (GM const float*)") + "out_ + i + j * " + std::to_string((int)out.ld) + "LL);\n  long long el = 0;\n";
+    src += loop("count");
+    src += std::string("  ") + (bf16 ? "st_bf16((GM unsigned short*)" : "st_f32((GM float*)") + "out_ + i + j * " + std::to_string((int)out.ld) + "LL, acc);\n}\n";
+  } else {
+    src += "  for (long long sl = blockIdx.y; sl < slices; sl += gridDim.y) {\n  const long long e1 = (sl + 1) * count / slices;\n  long long el = sl * count / slices;\n"
+           "  float acc[8]; _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) acc[e] = 0.0f;\n";
+    src += loop("e1");
+    src += "  st_f32((GM float*)part_ + (sl * " + std::to_string(N) + "LL + j) * " + std::to_string(M) + "LL + i, acc);\n  }\n}\n";
+  }
+}
+
+// The second kernel of the sliced form; it depends on the output's shape only.  One thread per 4 rows of a column (16-byte accesses):
+//   sum = part[0]; for (sl = 1; sl < slices; ++sl) sum = sum + part[sl];  out = out + sum
+// i.e. the partials in ascending slice order, then the output's original value.  No atomics anywhere: the same bits in every run.
+std::string generate_combine(int M, int N, int ldo, std::string& fname, long long& total) {
+  char buf[1536];
+  total = (long long)(M / 4) * N;
+  fname = "meqn_jit_combine_" + std::to_string(M) + "x" + std::to_string(N) + "_ld" + std::to_string(ldo);
+  std::snprintf(buf, sizeof(buf),
+    "#define GM __attribute__((address_space(1)))\ntypedef float f32x4 __attribute__((ext_vector_type(4)));\n"
+    "extern \"C\" __global__ __launch_bounds__(256) void %s(const void* part_, void* out_, long long slices) {\n"
+    "  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;\n  if (t >= %lldLL) return;\n  const long long j = t / %d, i = (t - j * %d) * 4;\n"
+    "  GM const float* part = (GM const float*)part_ + j * %dLL + i;\n"
+    "  f32x4 sum = *(GM const f32x4*)part;\n"
+    "  _Pragma(\"unroll 8\") for (long long sl = 1; sl < slices; ++sl) { const f32x4 p = *(GM const f32x4*)(part + sl * %lldLL); sum = sum + p; }\n"
+    "  GM f32x4* o = (GM f32x4*)((GM float*)out_ + i + j * %dLL);\n  const f32x4 a = *o;\n  *o = a + sum;\n}\n",
+    fname.c_str(), total, M / 4, M / 4, M, (long long)M * N, ldo);
+  return buf;
+}
+
 // returns false when the tree is not fusable; on success `src` holds the kernel source.
 // Two forms.  Element-wise trees: a grid of threads, one 8-row unit each.  Trees with reductions to ONE number inside (or as the head): one
 // workgroup of 256 threads that walks the units once per reduction ("phase"), folds its partial results in LDS and carries the number in a
@@ -297,7 +369,14 @@ bool scalar_reduce(const Equation& e, int id, int M, int N, ScalarReduce& r) {
 // `batched`: the form libxsmm_hip_meqn_batch_strided launches (name + "_b").  The same walk emits the same per-element code; the kernel takes one byte
 // stride per input, for `out` and per DUMP destination plus the element count, and steps every pointer by element * stride at entry.  Phased form: one
 // workgroup per element (grid-stride over elements beyond the grid); element-wise form: the element is the second grid dimension (grid-stride as well).
-bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eqn_idx, bool batched, std::string& src, std::string& fname, EqnPlan& plan, long long& total) {
+// FUSED_CARRIED / FUSED_SLICED: the forms libxsmm_hip_meqn_batch_strided_accumulate launches (element-wise trees only), see emit_accumulating.
+// `carried`: the input positions that alias the output.  In these two forms the leaf loads are collected apart from the arithmetic (`loads`), and every
+// name that belongs to one element carries the placeholder '@', which emit_accumulating replaces by the element's index inside the unrolled loop.
+bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eqn_idx, int form, const std::vector<int>& carried, std::string& src, std::string& fname, EqnPlan& plan, long long& total) {
+  const bool batched = form == FUSED_BATCHED, acc_form = form >= FUSED_CARRIED;
+  const char* U = acc_form ? "_@" : "";
+  std::string loads;
+  const auto is_carried = [&](int pos) { return acc_form && std::find(carried.begin(), carried.end(), pos) != carried.end(); };
   const EqnNode& root = e.nodes[0];
   const bool scalar_root = root.m == 1 && root.n == 1;
   int M = root.m, N = root.n;                      // the extent of the element-wise part: the head's, or (a head that is one number) the operands'
@@ -353,20 +432,26 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
     }
     if (bc == 0 && (ch.m != M || ch.n != N || ch.ld % 8 != 0)) return false;
     if (bc == 2 && ch.m != M) return false;
+    if (is_carried(ch.in_pos)) {      // the value the previous element left: this thread's own 8 rows (a broadcast would need another thread's); a sum's partial has no such leaf
+      if (bc != 0 || form == FUSED_SLICED) return false;
+      name = "a" + std::to_string(id) + U;
+      body += "  float " + name + "[8]; _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) " + name + "[e] = acc[e];\n";
+      return true;
+    }
     const int k = slot_of_arg(ch);
     if (k < 0) return false;
-    name = "a" + std::to_string(id);
+    name = "a" + std::to_string(id) + U;
     const char* T = ch.type == LIBXSMM_DATATYPE_F32 ? "float" : "unsigned short";
     const char* LD = ch.type == LIBXSMM_DATATYPE_F32 ? "ld_f32" : "ld_bf16";
     if (bc == 0 || bc == 2) {
-      std::snprintf(buf, sizeof(buf), "  float %s[8]; %s(%s, (GM const %s*)in%d + i%s);\n", name.c_str(), LD, name.c_str(), T, k,
+      std::snprintf(buf, sizeof(buf), "  float %s[8]; %s(%s, (GM const %s*)in%d%s + i%s);\n", name.c_str(), LD, name.c_str(), T, k, U,
                     bc == 0 ? (" + j * " + std::to_string(ch.ld) + "LL").c_str() : "");
     } else {
       const std::string idx = bc == 1 ? ("j * " + std::to_string(ch.ld) + "LL") : std::string("0");
-      if (ch.type == LIBXSMM_DATATYPE_F32) std::snprintf(buf, sizeof(buf), "  float %s[8]; { const float s = ((GM const float*)in%d)[%s]; _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) %s[e] = s; }\n", name.c_str(), k, idx.c_str(), name.c_str());
-      else std::snprintf(buf, sizeof(buf), "  float %s[8]; { const float s = __uint_as_float((unsigned int)((GM const unsigned short*)in%d)[%s] << 16); _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) %s[e] = s; }\n", name.c_str(), k, idx.c_str(), name.c_str());
+      if (ch.type == LIBXSMM_DATATYPE_F32) std::snprintf(buf, sizeof(buf), "  float %s[8]; { const float s = ((GM const float*)in%d%s)[%s]; _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) %s[e] = s; }\n", name.c_str(), k, U, idx.c_str(), name.c_str());
+      else std::snprintf(buf, sizeof(buf), "  float %s[8]; { const float s = __uint_as_float((unsigned int)((GM const unsigned short*)in%d%s)[%s] << 16); _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) %s[e] = s; }\n", name.c_str(), k, U, idx.c_str(), name.c_str());
     }
-    body += buf;
+    (acc_form ? loads : body) += buf;
     return true;
   };
 
@@ -377,7 +462,7 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
     const std::string v = "v" + std::to_string(id);
     if (nd.kind == EQ_UNARY) {
       if (nd.op == LIBXSMM_MELTW_TYPE_UNARY_DUMP) {      // identity that also lands in ops_args[pos].primary: an f32 M x N image, ld = M, below the head [ref: matequation ref :58-60]
-        if (id == 0 || nd.flags != 0 || nd.op_arg_pos < 0 || plan.fused_dumps.size() >= 4 || !operand(nd, 0, x, body)) return false;
+        if (acc_form || id == 0 || nd.flags != 0 || nd.op_arg_pos < 0 || plan.fused_dumps.size() >= 4 || !operand(nd, 0, x, body)) return false;
         const std::string d = "dump" + std::to_string(plan.fused_dumps.size());
         plan.fused_dumps.push_back(nd.op_arg_pos);
         body += "  float " + v + "[8];\n  _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) " + v + "[e] = " + x + "[e];\n  st_f32((GM float*)" + d + " + i + j * " + std::to_string(M) + "LL, " + v + ");\n";
@@ -483,14 +568,42 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
   };
 
   std::string body, head;
-  if (scalar_root) { if (M == 1 && N == 1) return false; if (!scalar_value(0, head)) return false; }
+  if (form == FUSED_SLICED) {
+    // out = acc + sum over the elements of g: the head is acc + x (BINARY_ADD, no broadcast) or acc + x * y (TERNARY_MULADD, the carried leaf as in2), and the
+    // carried leaf occurs nowhere in x, y (value() refuses it there).  The body adds one element's g to the running partial `acc`, the product rounded first as
+    // the single call rounds it.
+    if (scalar_root || out.type != LIBXSMM_DATATYPE_F32 || root.dtype != LIBXSMM_DATATYPE_F32) return false;
+    const auto leaf = [&](int c) { const EqnNode& ch = e.nodes[root.child[c]]; return ch.kind == EQ_ARG && is_carried(ch.in_pos); };
+    std::string x, y;
+    if (root.kind == EQ_BINARY && root.op == LIBXSMM_MELTW_TYPE_BINARY_ADD && root.flags == 0 && leaf(0) != leaf(1)) {
+      if (!value(root.child[leaf(0) ? 1 : 0], 0, x, body)) return false;
+      body += "  _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) acc[e] = acc[e] + " + x + "[e];\n";
+    } else if (root.kind == EQ_TERNARY && root.op == LIBXSMM_MELTW_TYPE_TERNARY_MULADD && (root.flags & ~(unsigned int)LIBXSMM_MELTW_FLAG_TERNARY_REUSE_IN_2_AS_OUT) == 0 && leaf(2)) {
+      if (!value(root.child[0], 0, x, body) || !value(root.child[1], 0, y, body)) return false;
+      body += "  _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) { const float prod = " + x + "[e] * " + y + "[e]; acc[e] = acc[e] + prod; }\n";
+    } else return false;
+  }
+  else if (scalar_root) { if (M == 1 && N == 1) return false; if (!scalar_value(0, head)) return false; }
   else if (!elem(0, body)) return false;
   const bool phased = scalar_root || !phases.empty();
+  if (acc_form && phased) return false;              // a reduction inside the tree couples the threads of an element: the element loop runs instead
   if (phased && units > 256 * 64) return false;      // one workgroup: beyond ~10^5 elements the chain of full-grid kernels is the faster form
   if (arg_types.empty() || arg_types.size() > 24) return false;
   total = phased ? 256 : units;
   fname = std::string(phased ? "meqn_jit_r" : "meqn_jit_e") + std::to_string(eqn_idx) + "_" + std::to_string(M) + "x" + std::to_string(N) + "_o" + std::to_string((int)out.type);
   if (batched) fname += "_b";
+  for (auto& a : arg_types) {
+    plan.fused_inputs.push_back(a.first);
+    char scalar = 0;
+    for (const EqnNode& nd : e.nodes) if (nd.kind == EQ_ARG && nd.in_pos == a.first && nd.m == 1 && nd.n == 1) scalar = 1;
+    plan.fused_scalar.push_back(scalar);
+    plan.fused_types.push_back(a.second);
+  }
+  if (acc_form) {
+    fname += form == FUSED_CARRIED ? "_c" : "_s";
+    emit_accumulating(form == FUSED_CARRIED, fname, units, M, N, out, arg_types.size(), plan.fused_alphas.size(), loads, body, src);
+    return true;
+  }
   const std::string sfx = batched ? "_" : "";        // batched: the arguments are the element-0 pointers, the names the body uses are the stepped ones
   src = kFusedPrelude;
   src += "extern \"C\" __global__ __launch_bounds__(256) void " + fname + "(";
@@ -526,20 +639,18 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
     if (batched) src += "  for (long long el = blockIdx.y; el < count; el += gridDim.y) {\n" + step + body + store + "  }\n}\n";
     else src += body + store + "}\n";
   }
-  for (auto& a : arg_types) {
-    plan.fused_inputs.push_back(a.first);
-    char scalar = 0;
-    for (const EqnNode& nd : e.nodes) if (nd.kind == EQ_ARG && nd.in_pos == a.first && nd.m == 1 && nd.n == 1) scalar = 1;
-    plan.fused_scalar.push_back(scalar);
-    plan.fused_types.push_back(a.second);
-  }
   return true;
 }
 
 }  // namespace
 
 const char* meqn_plan_name(const EqnPlan* plan) { return (plan && plan->fused) ? jit_name(plan->fused) : "meqn_tpp_chain"; }
-void free_meqn_plan(EqnPlan* plan) { if (plan && plan->fused) jit_release(plan->fused); if (plan && plan->fused_b) jit_release(plan->fused_b); delete plan; }
+void free_meqn_plan(EqnPlan* plan) {
+  if (plan && plan->fused) jit_release(plan->fused);
+  if (plan && plan->fused_b) jit_release(plan->fused_b);
+  if (plan) for (auto& f : plan->acc) { jit_release(f.second.carried); jit_release(f.second.sliced); jit_release(f.second.combine); }
+  delete plan;
+}
 // libxsmm_finalize: the equation objects (and their handle caches, whose handles the runtime has just released) go with the registry
 void free_meqn_equations() {
   std::lock_guard<std::mutex> guard(g_eqn_lock);
@@ -649,27 +760,31 @@ char* stage_span(const void* p, long long stride, size_t count, size_t bytes, bo
   char* base = result ? (char*)rt_small_host_output((char*)p + lo, span) : (char*)rt_small_host_input((const char*)p + lo, span);
   return base ? base - lo : nullptr;
 }
+// what every element shares must not be stepped: scalar op arguments (LEAKY_RELU's alpha), BRGEMM block counts, an UNZIP head's offset
+bool shared_not_stepped(const EqnPlan* plan, const long long* s_ops, int nops, long long s_aux) {
+  for (const EqnStep& st : plan->steps) {
+    if (stride_of(s_ops, nops, st.alpha_from_op) != 0 || stride_of(s_ops, nops, st.br_from_op) != 0) {
+      set_error(-3, "matrix equation batch: op argument %d is shared by all elements (a scalar / block count): its stride must be 0", st.alpha_from_op >= 0 ? st.alpha_from_op : st.br_from_op); return false;
+    }
+    if (st.root_side == 2 && s_aux != 0) { set_error(-3, "matrix equation batch: the UNZIP head's offset (output.secondary) is shared: stride_output_aux must be 0"); return false; }
+  }
+  for (int pos : plan->fused_alphas) if (stride_of(s_ops, nops, pos) != 0) { set_error(-3, "matrix equation batch: op argument %d (alpha) is shared: its stride must be 0", pos); return false; }
+  return true;
+}
 }  // namespace
 
 bool meqn_batch_prepare(EqnPlan* plan, const MeqnBatch& b) {
   if (b.count >= (1ull << 31)) { set_error(-2, "matrix equation batch: count %zu is not below 2^31", b.count); return false; }
   if (b.ninputs < plan->ninputs || (plan->ninputs > 0 && !b.s_in)) { set_error(-2, "matrix equation batch: %d input strides given, the equation reads %d input positions", b.ninputs, plan->ninputs); return false; }
   if (b.nops < 0) { set_error(-2, "matrix equation batch: negative number of op-argument strides"); return false; }
-  // what every element shares must not be stepped: scalar op arguments (LEAKY_RELU's alpha), BRGEMM block counts, an UNZIP head's offset
-  for (const EqnStep& st : plan->steps) {
-    if (stride_of(b.s_ops, b.nops, st.alpha_from_op) != 0 || stride_of(b.s_ops, b.nops, st.br_from_op) != 0) {
-      set_error(-3, "matrix equation batch: op argument %d is shared by all elements (a scalar / block count): its stride must be 0", st.alpha_from_op >= 0 ? st.alpha_from_op : st.br_from_op); return false;
-    }
-    if (st.root_side == 2 && b.s_aux != 0) { set_error(-3, "matrix equation batch: the UNZIP head's offset (output.secondary) is shared: stride_output_aux must be 0"); return false; }
-  }
-  for (int pos : plan->fused_alphas) if (stride_of(b.s_ops, b.nops, pos) != 0) { set_error(-3, "matrix equation batch: op argument %d (alpha) is shared: its stride must be 0", pos); return false; }
+  if (!shared_not_stepped(plan, b.s_ops, b.nops, b.s_aux)) return false;
   std::lock_guard<std::mutex> guard(g_eqn_lock);
   if (plan->fused && !plan->fused_b_tried) {
     plan->fused_b_tried = true;
     const Equation* e = get(plan->eqn_idx);
     std::string src, fname; long long total = 0;
     EqnPlan probe;
-    if (e && generate_fused(*e, plan->out_shape, plan->eqn_idx, true, src, fname, probe, total) && probe.fused_inputs == plan->fused_inputs &&
+    if (e && generate_fused(*e, plan->out_shape, plan->eqn_idx, FUSED_BATCHED, {}, src, fname, probe, total) && probe.fused_inputs == plan->fused_inputs &&
         probe.fused_alphas == plan->fused_alphas && probe.fused_dumps == plan->fused_dumps) {
       std::string why;
       plan->fused_b = jit_compile(src, fname, total, 16, &why);
@@ -821,6 +936,151 @@ const char* run_meqn_batch(EqnPlan* plan, const void* param, const MeqnBatch& b)
   }
   rt_finish_launch(err, kname ? kname : "meqn");
   return "meqn_tpp_chain";
+}
+
+
+// ---- accumulating strided batches (libxsmm_hip_meqn_batch_strided_accumulate) ------------------------------------------------------------------------------
+// Slices of the sliced form: a pure function of (count, M, N) -- never of the device's state -- so that the order of the additions, and with it every bit
+// of the result, is the same in every run, on every stream and in every process.  0: the carried form runs.
+// Rule (tools/bench_meqn_acc.py, profiles/r11_meqn_acc.jsonl): from kAccMinCount elements on (below, the second launch costs more
+// than the serial walk), a slice holds at least kAccMinSlice elements and the grid of ceil(M / 8 * N / 256) x S workgroups stays at or below kAccMaxGroups,
+// one per compute unit (every further slice is one more partial image for the combine kernel to read); fewer than 2 slices: the carried form.
+constexpr long long kAccMinCount = 128, kAccMinSlice = 16, kAccMaxGroups = 256;
+long long meqn_acc_slices(long long count, int M, int N) {
+  const long long blocks = ((long long)(M / 8) * N + 255) / 256;
+  const long long s = std::min(count / kAccMinSlice, std::max<long long>(1, kAccMaxGroups / blocks));
+  return (count >= kAccMinCount && s >= 2) ? s : 0;
+}
+
+bool meqn_acc_prepare(EqnPlan* plan, const void* param, const MeqnAcc& b, std::vector<int>& carried) {
+  const libxsmm_meqn_param* p = (const libxsmm_meqn_param*)param;
+  if (b.count >= (1ull << 31)) { set_error(-2, "matrix equation batch: count %zu is not below 2^31", b.count); return false; }
+  if (b.ninputs < plan->ninputs || (plan->ninputs > 0 && !b.s_in)) { set_error(-2, "matrix equation batch: %d input strides given, the equation reads %d input positions", b.ninputs, plan->ninputs); return false; }
+  if (b.nops < 0) { set_error(-2, "matrix equation batch: negative number of op-argument strides"); return false; }
+  if (b.order != LIBXSMM_HIP_MEQN_ORDER_LOOP && b.order != LIBXSMM_HIP_MEQN_ORDER_ANY) { set_error(-3, "accumulating matrix equation batch: unknown order %d", b.order); return false; }
+  if (!p->inputs || !p->output.primary) { set_error(-2, "matrix equation called without inputs / output"); return false; }
+  if (!shared_not_stepped(plan, b.s_ops, b.nops, 0)) return false;
+  for (const EqnStep& st : plan->steps) {
+    if (st.root_side != 0) { set_error(-3, "accumulating matrix equation batch: the head writes a side channel (output.secondary) per call"); return false; }
+    if (st.dump_from_op >= 0 && b.count > 1 && stride_of(b.s_ops, b.nops, st.dump_from_op) == 0) {
+      set_error(-3, "accumulating matrix equation batch: the DUMP destination (op argument %d) needs a stride: every element would write the same image", st.dump_from_op); return false;
+    }
+  }
+  std::lock_guard<std::mutex> guard(g_eqn_lock);
+  const Equation* e = get(plan->eqn_idx);
+  if (!e) { set_error(-3, "accumulating matrix equation batch: the equation of this handle is gone"); return false; }
+  // the carried operand(s): input positions of the tree that ARE the output (same address, not stepped)
+  carried.clear();
+  const libxsmm_meqn_arg_shape& o = plan->out_shape;
+  for (int pos = 0; pos < plan->ninputs; ++pos) {
+    if (p->inputs[pos].primary != p->output.primary || b.s_in[pos] != 0) continue;
+    bool used = false;
+    for (const EqnNode& nd : e->nodes) if (nd.kind == EQ_ARG && nd.in_pos == pos) {
+      used = true;
+      if (nd.m != o.m || nd.n != o.n || nd.ld != o.ld || nd.type != (int)o.type) {
+        set_error(-3, "accumulating matrix equation batch: input %d is the output but was declared %d x %d, ld %d, type %d", pos, nd.m, nd.n, nd.ld, nd.type); return false;
+      }
+    }
+    if (used) carried.push_back(pos);
+  }
+  if (carried.empty()) { set_error(-3, "accumulating matrix equation batch: no input position is the output (same pointer, stride 0): nothing is carried from element to element"); return false; }
+  if (!plan->fused || std::strncmp(jit_name(plan->fused), "meqn_jit_e", 10) != 0) return true;      // phased / chain-only trees: the element loop
+  const bool fresh = plan->acc.find(carried) == plan->acc.end();
+  EqnPlan::AccForms& f = plan->acc[carried];
+  const auto make = [&](int form, JitKernel*& k, std::vector<int>& inputs, std::vector<char>& scalar, std::vector<int>& types) {
+    std::string src, fname, why; long long total = 0;
+    EqnPlan probe;
+    if (!generate_fused(*e, plan->out_shape, plan->eqn_idx, form, carried, src, fname, probe, total) || probe.fused_alphas != plan->fused_alphas) return;
+    k = jit_compile(src, fname, total, 16, &why);
+    inputs = probe.fused_inputs; scalar = probe.fused_scalar; types = probe.fused_types;
+    if (!k && std::getenv("LIBXSMM_HIP_JIT_VERBOSE")) std::fprintf(stderr, "libxsmm_amd: generated accumulating equation kernel did not compile: %s\n%s\n", why.c_str(), src.c_str());
+  };
+  if (fresh) make(FUSED_CARRIED, f.carried, f.c_inputs, f.c_scalar, f.c_types);
+  if (b.order == LIBXSMM_HIP_MEQN_ORDER_ANY && !f.sliced_tried) {
+    f.sliced_tried = true;
+    make(FUSED_SLICED, f.sliced, f.s_inputs, f.s_scalar, f.s_types);
+    if (f.sliced) {
+      std::string fname, why; long long total = 0;
+      const std::string src = generate_combine(o.m, o.n, o.ld, fname, total);
+      f.combine = jit_compile(src, fname, total, 16, &why);
+      if (!f.combine && std::getenv("LIBXSMM_HIP_JIT_VERBOSE")) std::fprintf(stderr, "libxsmm_amd: generated combine kernel did not compile: %s\n%s\n", why.c_str(), src.c_str());
+    }
+  }
+  return true;
+}
+
+const char* run_meqn_acc(EqnPlan* plan, const void* param, const MeqnAcc& b, const std::vector<int>& carried) {
+  const libxsmm_meqn_param* p = (const libxsmm_meqn_param*)param;
+  const size_t count = b.count;
+  rt_scratch_reset();
+  const auto hit = plan->acc.find(carried);
+  const EqnPlan::AccForms* f = hit != plan->acc.end() ? &hit->second : nullptr;
+  if (f && f->carried && jit_on_current_device(f->carried)) {
+    const int M = plan->out_shape.m, N = plan->out_shape.n;
+    long long slices = 0;
+    if (b.order == LIBXSMM_HIP_MEQN_ORDER_ANY && f->sliced && f->combine && jit_on_current_device(f->sliced) && jit_on_current_device(f->combine)) {
+      slices = meqn_acc_slices((long long)count, M, N);
+      // LIBXSMM_HIP_MEQN_ACC_SLICES=<S> (measurements only): S slices whatever the rule says, 0 = the carried form
+      if (const char* v = std::getenv("LIBXSMM_HIP_MEQN_ACC_SLICES")) slices = std::min<long long>(std::max(0ll, std::atoll(v)), (long long)count);
+    }
+    const bool sliced = slices > 0;
+    const std::vector<int>& inputs = sliced ? f->s_inputs : f->c_inputs;
+    const std::vector<char>& scalar = sliced ? f->s_scalar : f->c_scalar;
+    const std::vector<int>& types = sliced ? f->s_types : f->c_types;
+    const void* ptrs[24]; long long strides[24]; float alphas[8]; void* args[2 * 24 + 1 + 8 + 2]; int na = 0; bool ok = true;
+    for (size_t i = 0; i < inputs.size(); ++i) {
+      const int pos = inputs[i];
+      ptrs[i] = p->inputs[pos].primary; strides[i] = b.s_in[pos];
+      if (ptrs[i] && scalar[i]) { ptrs[i] = stage_span(ptrs[i], b.s_in[pos], count, (size_t)typesize(types[i]), false); if (!ptrs[i]) return nullptr; }
+      ok = ok && ptrs[i] && (scalar[i] || ((((size_t)ptrs[i]) | (size_t)b.s_in[pos]) & 15) == 0);
+      args[na++] = (void*)&ptrs[i];
+    }
+    void* outp = p->output.primary;
+    ok = ok && (((size_t)outp) & 15) == 0;
+    void* part = nullptr;
+    if (ok && sliced) { part = rt_workspace((size_t)slices * (size_t)M * (size_t)N * 4); if (!part) return nullptr; }
+    args[na++] = sliced ? (void*)&part : (void*)&outp;
+    for (size_t i = 0; i < plan->fused_alphas.size() && ok; ++i) {
+      if (!p->ops_args || !p->ops_args[plan->fused_alphas[i]].primary) { set_error(-2, "matrix equation: op argument %d is NULL", plan->fused_alphas[i]); return nullptr; }
+      alphas[i] = *(const float*)p->ops_args[plan->fused_alphas[i]].primary; args[na++] = (void*)&alphas[i];
+    }
+    if (ok) {
+      long long n = (long long)count;
+      for (size_t i = 0; i < inputs.size(); ++i) args[na++] = (void*)&strides[i];
+      args[na++] = (void*)&n;
+      if (!sliced) {
+        rt_finish_launch(jit_launch(f->carried, args, rt_stream()), jit_name(f->carried));
+        return jit_name(f->carried);
+      }
+      args[na++] = (void*)&slices;
+      const unsigned int gx = (unsigned int)(((long long)(M / 8) * N + 255) / 256), gy = (unsigned int)std::min<long long>(slices, 65535);
+      const int err = jit_launch_grid(f->sliced, args, gx, gy, rt_stream());
+      rt_nest(+1); rt_finish_launch(err, jit_name(f->sliced)); rt_nest(-1);          // two launches in stream order; synchronised once, behind the second
+      if (err != 0) return nullptr;
+      void* cargs[3] = {(void*)&part, (void*)&outp, (void*)&slices};
+      rt_finish_launch(jit_launch(f->combine, cargs, rt_stream()), jit_name(f->combine));
+      return jit_name(f->sliced);
+    }
+  }
+  // everything else: the elements one after another through the single-call path, each in the thread's launch mode -- the caller's loop
+  int nops = 0;
+  for (const EqnStep& st : plan->steps) nops = std::max(nops, std::max(st.alpha_from_op, std::max(st.dump_from_op, st.br_from_op)) + 1);
+  for (int pos : plan->fused_alphas) nops = std::max(nops, pos + 1);
+  for (int pos : plan->fused_dumps) nops = std::max(nops, pos + 1);
+  std::vector<libxsmm_matrix_arg> in(p->inputs, p->inputs + plan->ninputs);
+  std::vector<libxsmm_matrix_op_arg> ops;
+  if (p->ops_args && nops > 0) ops.assign(p->ops_args, p->ops_args + nops);
+  const int err_before = libxsmm_hip_get_last_error();
+  for (size_t i = 0; i < count; ++i) {
+    libxsmm_meqn_param q = *p;
+    for (int k = 0; k < plan->ninputs; ++k) if (p->inputs[k].primary) in[(size_t)k].primary = (char*)p->inputs[k].primary + (long long)i * b.s_in[k];
+    for (int k = 0; k < nops && !ops.empty(); ++k) if (p->ops_args[k].primary) ops[(size_t)k].primary = (char*)p->ops_args[k].primary + (long long)i * stride_of(b.s_ops, b.nops, k);
+    q.inputs = in.data(); if (!ops.empty()) q.ops_args = ops.data();
+    rt_scratch_reset();
+    run_meqn(plan, &q);
+    if (libxsmm_hip_get_last_error() != err_before) return nullptr;      // an element failed: the rest would build on its result
+  }
+  return meqn_plan_name(plan);
 }
 
 }  // namespace xamd
@@ -1020,7 +1280,7 @@ LIBXSMM_API libxsmm_meqn_function libxsmm_dispatch_meqn(libxsmm_blasint idx, lib
   if (rt_jit_mode() != 0) {     // element-wise trees: one generated kernel instead of one launch per node
     std::string src, fname; long long total = 0;
     EqnPlan probe;
-    if (generate_fused(*e, out, idx, false, src, fname, probe, total)) {
+    if (generate_fused(*e, out, idx, FUSED_SINGLE, {}, src, fname, probe, total)) {
       std::string why;
       plan->fused = jit_compile(src, fname, total, 16, &why);
       if (!plan->fused && std::getenv("LIBXSMM_HIP_JIT_VERBOSE")) std::fprintf(stderr, "libxsmm_amd: generated equation kernel did not compile: %s\n%s\n", why.c_str(), src.c_str());

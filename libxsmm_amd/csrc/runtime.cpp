@@ -2211,6 +2211,17 @@ LIBXSMM_API void libxsmm_hip_meqn_batch_strided(libxsmm_meqn_function kernel, co
   scratch_reset();
   if (const char* kname = run_meqn_batch(c->eqn, param, b)) c->kname_batched = kname;
 }
+LIBXSMM_API void libxsmm_hip_meqn_batch_strided_accumulate(libxsmm_meqn_function kernel, const libxsmm_meqn_param* param, size_t count,
+  int ninputs, const long long* stride_inputs, int nops_args, const long long* stride_ops_args, int order) {
+  KernelCtx* c = batch_ctx((const void*)kernel, K_MEQN); if (!c || !param || count == 0) return;
+  const MeqnAcc b{count, ninputs, stride_inputs, nops_args, stride_ops_args, order};
+  std::vector<int> carried;
+  if (!meqn_acc_prepare(c->eqn, param, b, carried)) return;      // as the strided entry: validation and code generation before the device is needed
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  if (const char* kname = run_meqn_acc(c->eqn, param, b, carried)) c->kname_batched = kname;
+}
 // ---- grouped batches (libxsmm_hip_gemm_batch_grouped): several shapes, one launch per precision class --------------------------------------------------
 // A group enters the grouped kernels (gemm_grouped_kernels.hip) when its handle is a plain GEMM or a STRIDE batch-reduce handle of f32 x f32 -> f32 or
 // bf16 x bf16 -> f32 / bf16 (A flat or VNNI-2, B flat, C not VNNI), NN, with no flag beyond beta and the hints; `cls` = 0 (f32) or 1 (bf16).
