@@ -204,6 +204,33 @@ typedef struct libxsmm_hip_gemm_group {
   long long            stride_a, stride_b, stride_c;   /* byte strides of the primary slots; 0 = shared (weights) */
 } libxsmm_hip_gemm_group;
 LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* groups, size_t ngroups);
+/**
+ * Segments: a batch of ADDRESS batch-reduce calls whose reduce count differs from call to call -- the count is the one argument the reference re-reads on
+ * every call [ref: src/generator_gemm_reference_impl.c:490-492] -- as ONE launch: a block-sparse matrix times a dense one (one BRGEMM per block row of C),
+ * a stack of small products accumulating into blocks of C, a convolution whose border pixels see fewer taps.  `kernel` is an ADDRESS batch-reduce handle
+ * (libxsmm_dispatch_brgemm with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS):
+ *   libxsmm_hip_gemm_batch_reduce_segments(kernel, param, nsegments, seg_ptr, a_list, b_list, c_list)
+ *     ==  for (s = 0; s < nsegments; ++s) { q = *param; cnt = seg_ptr[s+1] - seg_ptr[s];
+ *           q.a.primary = (void*)(a_list + seg_ptr[s]);  q.b.primary = (void*)(b_list + seg_ptr[s]);
+ *           q.c.primary = c_list[s];  q.op.tertiary = &cnt;  kernel(&q); }
+ * seg_ptr holds nsegments + 1 entries, CSR-style and non-decreasing; a_list and b_list hold seg_ptr[nsegments] block pointers each, c_list nsegments.  All
+ * four arrays must be device-accessible, like the lists of libxsmm_hip_gemm_batch_pointers: nothing is staged or uploaded per call, so a caller whose
+ * pattern is fixed pays nothing on the host beyond the launch, and the call may be captured into a graph.  param's primary slots and op.tertiary are
+ * ignored.  Segments whose C blocks overlap are undefined; A and B blocks may be shared freely between products and segments.  Within a segment the
+ * products are summed in list order: starting from C (beta = 1) or +0 they form one accumulator chain over (product, k), as in the reference; for f32 the
+ * result is the k-ordered fmaf chain bit for bit.  A segment of count 0 is the reference's call with a count of 0: beta = 0 sets the m x n block to +0,
+ * beta = 1 leaves it untouched.  Work is handed to the device in list order (a work item is a segment's C tile, taken up in ascending order): a caller who
+ * lists long segments first gets longest-first scheduling for free; a segment is never split, which would reorder its sum.
+ * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16; A flat (or VNNI_A for bf16), B flat, C not VNNI, no transposes; beta 0
+ * or 1; no flag beyond those and the hints; any m, n, k and leading dimensions whose element offsets inside an operand stay below 2^31.  Block pointers
+ * need element alignment only.  Follows the thread's launch mode: blocking (returns when done), stream-ordered, coalescing (the queue is flushed first),
+ * inside a pipeline section (the launch goes to a lane).  Errors are set before anything is launched.  -2: param, seg_ptr, a_list, b_list or c_list is NULL
+ * while nsegments > 0; -3: an unknown handle, a TPP / equation / sparse / ext handle, a GEMM handle that is not ADDRESS batch-reduce, or a type, layout or
+ * flag outside the list above (the message names which); -4: no device.  nsegments = 0 does nothing.  libxsmm_hip_kernel_name(kernel, 1) names the
+ * kernel that ran (gemm_segments_f32_kernel, _f64_kernel, _bf16_kernel).
+ */
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
+  size_t nsegments, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list);
 
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns

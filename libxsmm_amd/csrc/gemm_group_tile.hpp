@@ -1,0 +1,298 @@
+// gemm_group_tile.hpp -- the one-wave C tiles shared by the grouped kernels (gemm_grouped_kernels.hip) and the segment kernels
+// (gemm_segments_kernels.hip): a wave owns a T x T tile of C (T = 32 or 16) and walks a CHAIN of (A, B) block pairs, one accumulator over (block, k).
+// Where the blocks of the chain lie is the only thing the two users differ in, so it is a template parameter:
+//   StrideChain   block r = base + r * stride                                   (STRIDE batch-reduce; count 1 for plain GEMM handles)
+//   ListChain     block r = a_list[r], b_list[r], read with scalar loads         (ADDRESS batch-reduce with a count of its own per segment)
+// A chain hands out block r + 1 while block r is being multiplied (fetch), so a list chain's dependent address -> data round trip overlaps the MFMAs, and it
+// answers the alignment questions of the wider loads per block (a stride chain answers with what the host worked out for the whole group).
+//
+// Both operands enter the MFMA swapped (B as the first operand, A as the second), as gemm_tile.hpp does: the accumulator then holds a column of C per register
+// and the ROWS of C on the lanes, so every store of a register is a contiguous run of 16 or 32 rows.
+//   f32 : v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 with k in natural order -- the result is the k-ordered fmaf chain bit for bit
+//         (cdna_hip_programming.md, "FP32-input MFMA"), which is what oracle_gemm_f32_fma computes [ref: src/generator_gemm_reference_impl.c:1359-1426].
+//   bf16: v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x16_bf16, A flat or VNNI-2, B flat, C f32 or bf16 (bf16_cvt.hpp: the reference's conversion exactly).
+//   f64 : v_mfma_f64_16x16x4_f64, T = 16 only, k in natural order, four k per instruction [ref: src/generator_gemm_reference_impl.c:1322-1358].
+// beta = 1 starts the chain at C.  Ragged k is padded with A = -0.0 and B = +0.0: adding the product -0 is an exact identity for every accumulator
+// (+0 + -0 = +0 under round-to-nearest), so the f32 chain stays bitwise.  Rows and columns beyond m / n load the last valid row / column and are never
+// stored, so no access leaves the caller's operands.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "internal.hpp"
+#include "gemm_device.hpp"
+#include "bf16_cvt.hpp"
+
+namespace xamd {
+namespace group_tile {
+
+struct StrideChain {
+  gcptr a, b; long long sa, sb; unsigned long long count;
+  int va4, vb16, vb8;                              // the host's verdict for every block of the group (GemmGroupDesc::a_vec4 / b_vec16 / b_vec8)
+  __device__ __forceinline__ void fetch(unsigned long long r, gcptr& pa, gcptr& pb) const { pa = a + (long long)r * sa; pb = b + (long long)r * sb; }
+  __device__ __forceinline__ bool a_vec4(gcptr) const { return va4 != 0; }
+  __device__ __forceinline__ bool b_vec16(gcptr) const { return vb16 != 0; }
+  __device__ __forceinline__ bool b_vec8(gcptr) const { return vb8 != 0; }
+};
+__device__ __forceinline__ StrideChain stride_chain(const GemmGroupDesc& g, gcptr a, gcptr b) {
+  return StrideChain{a, b, g.br_sa, g.br_sb, g.br_count, g.a_vec4, g.b_vec16, g.b_vec8};
+}
+
+// `la` / `lb` point at the chain's first list entry.  The lists are only read at entries < count: fetch(count) re-reads the last entry, whose value is dropped.
+// A block pointer is only known to be element-aligned, so the wider loads are chosen per block by a wave-uniform test of the pointer; `va4` / `vb16` / `vb8`
+// say whether the leading dimension allows them at all.
+struct ListChain {
+  const void* la; const void* lb; unsigned long long count;
+  int va4, vb16, vb8;
+  __device__ __forceinline__ void fetch(unsigned long long r, gcptr& pa, gcptr& pb) const {
+    const unsigned long long rc = r < count ? r : count - 1;
+    pa = list_entry(la, rc); pb = list_entry(lb, rc);
+  }
+  __device__ __forceinline__ bool a_vec4(gcptr p) const { return va4 != 0 && ((unsigned int)(size_t)p & 3u) == 0; }
+  __device__ __forceinline__ bool b_vec16(gcptr p) const { return vb16 != 0 && ((unsigned int)(size_t)p & 15u) == 0; }
+  __device__ __forceinline__ bool b_vec8(gcptr p) const { return vb8 != 0 && ((unsigned int)(size_t)p & 7u) == 0; }
+};
+
+// accumulator register r of lane `lane` holds C column (j0 +) acc_col<T>(r, lane), C row (i0 +) lane % T
+template <int T> __device__ __forceinline__ int acc_col(int r, unsigned int lane) {
+  if constexpr (T == 32) return (r & 3) + 8 * (r >> 2) + 4 * (int)(lane >> 5);
+  else return 4 * (int)(lane >> 4) + r;
+}
+
+typedef short bf16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+template <int T> struct Acc;
+template <> struct Acc<32> { typedef f32x16 type; static constexpr int N = 16; };
+template <> struct Acc<16> { typedef f32x4 type; static constexpr int N = 4; };
+
+__device__ __forceinline__ f32x16 mfma_f32(float x, float y, f32x16 acc) { return __builtin_amdgcn_mfma_f32_32x32x2f32(x, y, acc, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma_f32(float x, float y, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, acc, 0, 0, 0); }
+
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned short v) { return __uint_as_float((unsigned int)v << 16); }
+
+// the accumulator's start value: C (beta = 1) or +0
+template <int T> __device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& g, gptr c, int i, int j0, bool mv, unsigned int lane) {
+  typename Acc<T>::type acc;
+  static_for<Acc<T>::N>([&](auto r) {
+    const int j = j0 + acc_col<T>(r, lane);
+    float v = 0.0f;
+    if (g.beta1 && mv && j < g.n) {
+      const long long o = (long long)j * g.ldc + i;
+      v = g.c_bf16 ? bf16_bits_to_f32(((GM const unsigned short*)c)[o]) : ((GM const float*)c)[o];
+    }
+    acc[r.value] = v;
+  });
+  return acc;
+}
+
+template <int T> __device__ __forceinline__ void acc_store(const GemmGroupDesc& g, gptr c, typename Acc<T>::type acc, int i, int j0, bool mv, unsigned int lane) {
+  constexpr int N = Acc<T>::N;
+  if (g.c_bf16) {
+    float x[N]; unsigned int pk[N / 2];
+    static_for<N>([&](auto r) { x[r] = acc[r.value]; });
+    bf16_pk_exact_n<N / 2>(x, pk);
+    static_for<N>([&](auto r) {
+      const int j = j0 + acc_col<T>(r, lane);
+      if (mv && j < g.n) ((GM unsigned short*)c)[(long long)j * g.ldc + i] = (unsigned short)((r & 1) ? (pk[r / 2] >> 16) : (pk[r / 2] & 0xffffu));
+    });
+  } else {
+    static_for<N>([&](auto r) {
+      const int j = j0 + acc_col<T>(r, lane);
+      if (mv && j < g.n) ((GM float*)c)[(long long)j * g.ldc + i] = acc[r.value];
+    });
+  }
+}
+
+// U consecutive MFMA steps of an f32 tile from k = kk on: all operand requests of the steps go out before the first MFMA, so a block of U steps pays the
+// memory latency once.  b_vec: B(kk .. kk + 2 U - 1) of the lane's column in 16-byte pieces (32-tiles); lane half h takes the odd or even k of a piece.
+template <int T, int U> __device__ __forceinline__ void steps_f32(typename Acc<T>::type& acc, GM const float* ap, GM const float* bp, int kk, int lda, int h, bool b_vec) {
+  constexpr int KS = (T == 32) ? 2 : 4;
+  float av[U], bv[U];
+#pragma unroll
+  for (int s = 0; s < U; ++s) av[s] = ap[(kk + s * KS + h) * lda];
+  if (T == 32 && b_vec) {
+#pragma unroll
+    for (int q = 0; q < U / 2; ++q) {
+      const f32x4 v = *(GM const f32x4*)(bp + kk + 4 * q);
+      bv[2 * q] = h ? v[1] : v[0]; bv[2 * q + 1] = h ? v[3] : v[2];
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < U; ++s) bv[s] = bp[kk + s * KS + h];
+  }
+#pragma unroll
+  for (int s = 0; s < U; ++s) acc = mfma_f32(bv[s], av[s], acc);
+}
+
+// one C tile of T x T of an f32 element: lane (i = lane % T, h = lane / T) feeds A(i, k0 + h) and B(k0 + h, j0 + lane % T) per MFMA.
+// Loads carry no predicate (a predicated load is a branch around it in the code): rows / columns beyond m / n read the last valid row / column -- in bounds,
+// never stored -- and k beyond K reads k = K - 1 and replaces the value by the -0 / +0 padding.  k advances in blocks of 4 MFMA steps, then one block of up to
+// 4 ragged steps; DEEP puts blocks of 16 steps in front (32 k on a 32-tile: a 32^3 block is ONE round of requests, at 72 more registers) for the kernels
+// whose waves walk long chains alone (segments).  The MFMAs always follow k in natural order.
+template <int T, bool DEEP, typename Chain> __device__ __forceinline__ void tile_f32(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
+  constexpr int KS = (T == 32) ? 2 : 4;
+  const int lr = (int)(lane & (T - 1)), h = (int)(lane / T);
+  const int i = i0 + lr, j = j0 + lr;
+  const bool mv = i < g.m;
+  typename Acc<T>::type acc = acc_start<T>(g, c, i, j0, mv, lane);
+  const int K = g.k, lda = g.lda;
+  const int kbig = K - K % (16 * KS), kfull = K - K % (4 * KS);
+  gcptr an = nullptr, bn = nullptr;
+  if (ch.count) ch.fetch(0, an, bn);
+  for (unsigned long long r = 0; r < ch.count; ++r) {
+    const gcptr a = an, b = bn;
+    ch.fetch(r + 1, an, bn);                   // the next block's addresses are on their way while this block is multiplied
+    GM const float* ap = (GM const float*)a + min(i, g.m - 1);
+    GM const float* bp = (GM const float*)b + (long long)min(j, g.n - 1) * g.ldb;
+    const bool b_vec = T == 32 && ch.b_vec16(b);
+    int kk = 0;
+    if constexpr (DEEP) for (; kk < kbig; kk += 16 * KS) steps_f32<T, 16>(acc, ap, bp, kk, lda, h, b_vec);
+    for (; kk < kfull; kk += 4 * KS) steps_f32<T, 4>(acc, ap, bp, kk, lda, h, b_vec);
+    if (kk < K) {                              // ragged k, up to four steps: A = -0, B = +0 beyond K
+      float av[4], bv[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int kx = kk + s * KS + h, kc = min(kx, K - 1);
+        const float va = ap[kc * lda], vb = bp[kc];
+        av[s] = kx < K ? va : -0.0f; bv[s] = kx < K ? vb : 0.0f;
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (kk + s * KS < K) acc = mfma_f32(bv[s], av[s], acc);
+    }
+  }
+  acc_store<T>(g, c, acc, i, j0, mv, lane);
+}
+
+// bf16: lane (i = lane % T, h = lane / T) feeds A(i, k0 + E h + e) and B(k0 + E h + e, j0 + lane % T), e < E, per MFMA: E = 8 for the 32 x 32 x 16
+// instruction, E = 4 for the 16 x 16 x 16 one (a 16-deep k step: a 16^3 problem is one whole step, no padding)
+__device__ __forceinline__ unsigned short a_bf16(const GemmGroupDesc& g, GM const unsigned short* ap, int i, int kx) {
+  return g.vnni_a ? ap[((long long)(kx >> 1) * g.lda + i) * 2 + (kx & 1)] : ap[(long long)kx * g.lda + i];
+}
+template <int E> struct Frag;
+template <> struct Frag<8> { typedef bf16x8 type; typedef u32x4 words; };
+template <> struct Frag<4> { typedef bf16x4 type; typedef u32x2 words; };
+__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 x, bf16x8 y, f32x16 acc) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma_bf16(bf16x4 x, bf16x4 y, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(x, y, acc, 0, 0, 0); }
+// U consecutive MFMA steps (16 k each) of a bf16 tile from k = kk on, every operand request ahead of the first MFMA; VEC: both operands are known to take
+// the wide loads (no element-wise code in the instance)
+template <int T, int U, bool VEC> __device__ __forceinline__ void steps_bf16(const GemmGroupDesc& g, typename Acc<T>::type& acc, GM const unsigned short* ap, GM const unsigned short* bp,
+  int kk, int il, int h, bool a_vec, bool b_vec) {
+  constexpr int E = (T == 32) ? 8 : 4, KS = 16;
+  typedef typename Frag<E>::type frag;
+  typedef typename Frag<E>::words words;
+  frag x[U], y[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int k0 = kk + u * KS + E * h;
+    if (VEC || b_vec) x[u] = __builtin_bit_cast(frag, *(GM const words*)(bp + k0));
+    else {
+#pragma unroll
+      for (int e = 0; e < E; ++e) x[u][e] = (short)bp[k0 + e];
+    }
+    if (VEC || a_vec) {
+      GM const unsigned int* ap4 = (GM const unsigned int*)ap;
+      words w;
+#pragma unroll
+      for (int e = 0; e < E / 2; ++e) w[e] = ap4[(long long)((k0 >> 1) + e) * g.lda + il];
+      y[u] = __builtin_bit_cast(frag, w);
+    } else {
+#pragma unroll
+      for (int e = 0; e < E; ++e) y[u][e] = (short)a_bf16(g, ap, il, k0 + e);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) acc = mfma_bf16(x[u], y[u], acc);
+}
+template <int T, bool DEEP, typename Chain> __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
+  constexpr int E = (T == 32) ? 8 : 4, KS = 16;
+  typedef typename Frag<E>::type frag;
+  const int lr = (int)(lane & (T - 1)), h = (int)(lane / T);
+  const int i = i0 + lr, j = j0 + lr;
+  const bool mv = i < g.m;
+  const int il = min(i, g.m - 1);
+  typename Acc<T>::type acc = acc_start<T>(g, c, i, j0, mv, lane);
+  const int K = g.k;
+  const int kbig = K - K % (4 * KS), kfull = K - K % KS;
+  gcptr an = nullptr, bn = nullptr;
+  if (ch.count) ch.fetch(0, an, bn);
+  for (unsigned long long r = 0; r < ch.count; ++r) {
+    const gcptr a = an, b = bn;
+    ch.fetch(r + 1, an, bn);
+    GM const unsigned short* ap = (GM const unsigned short*)a;
+    GM const unsigned short* bp = (GM const unsigned short*)b + (long long)min(j, g.n - 1) * g.ldb;
+    const bool b_vec = (T == 32) ? ch.b_vec16(b) : ch.b_vec8(b);
+    const bool a_vec = g.vnni_a && ch.a_vec4(a);
+    int kk = 0;
+    if constexpr (DEEP) {                      // segments: 64 k per round of requests when both operands take the wide loads (32 more registers)
+      if (a_vec && b_vec) for (; kk < kbig; kk += 4 * KS) steps_bf16<T, 4, true>(g, acc, ap, bp, kk, il, h, true, true);
+    }
+    for (; kk < kfull; kk += KS) steps_bf16<T, 1, false>(g, acc, ap, bp, kk, il, h, a_vec, b_vec);
+    if (kk < K) {                              // ragged k: A = -0 (0x8000), B = +0 beyond K
+      const int k0 = kk + E * h;
+      frag x, y;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int kx = k0 + e, kc = min(kx, K - 1);
+        const unsigned short vb = bp[kc], va = a_bf16(g, ap, il, kc);
+        x[e] = (short)(kx < K ? vb : 0);
+        y[e] = (short)(kx < K ? va : 0x8000);
+      }
+      acc = mfma_bf16(x, y, acc);
+    }
+  }
+  acc_store<T>(g, c, acc, i, j0, mv, lane);
+}
+
+// f64, one 16 x 16 tile: lane (g = lane % 16, s = lane / 16) feeds A(i0 + g, k0 + s) and B(k0 + s, j0 + g) per MFMA and holds C(i0 + g, j0 + s + 4 r) in
+// register pair r (the f64 instruction's own map, gemm_f64_kernels.hip).  Same clamping and padding as the f32 tile; k advances in blocks of 32, then 16, then one
+// block of up to four ragged steps, every request of a block in flight before its MFMAs.
+template <int U> __device__ __forceinline__ void steps_f64(f64x4& acc, GM const double* ap, GM const double* bp, int kk, int lda, int s) {
+  double av[U], bv[U];
+#pragma unroll
+  for (int e = 0; e < U; ++e) av[e] = ap[(kk + 4 * e + s) * lda];
+#pragma unroll
+  for (int e = 0; e < U; ++e) bv[e] = bp[kk + 4 * e + s];
+#pragma unroll
+  for (int e = 0; e < U; ++e) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[e], av[e], acc, 0, 0, 0);
+}
+template <typename Chain> __device__ __forceinline__ void tile_f64(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
+  const int lr = (int)(lane & 15u), s = (int)(lane >> 4);
+  const int i = i0 + lr, j = j0 + lr;
+  const bool mv = i < g.m;
+  f64x4 acc;
+  static_for<4>([&](auto r) {
+    const int jc = j0 + s + 4 * r.value;
+    acc[r.value] = (g.beta1 && mv && jc < g.n) ? ((GM const double*)c)[(long long)jc * g.ldc + i] : 0.0;
+  });
+  const int K = g.k, lda = g.lda;
+  const int kbig = K - K % 32, kfull = K - K % 16;
+  gcptr an = nullptr, bn = nullptr;
+  if (ch.count) ch.fetch(0, an, bn);
+  for (unsigned long long r = 0; r < ch.count; ++r) {
+    const gcptr a = an, b = bn;
+    ch.fetch(r + 1, an, bn);
+    GM const double* ap = (GM const double*)a + min(i, g.m - 1);
+    GM const double* bp = (GM const double*)b + (long long)min(j, g.n - 1) * g.ldb;
+    int kk = 0;
+    for (; kk < kbig; kk += 32) steps_f64<8>(acc, ap, bp, kk, lda, s);
+    for (; kk < kfull; kk += 16) steps_f64<4>(acc, ap, bp, kk, lda, s);
+    if (kk < K) {                              // ragged k, up to four steps: A = -0, B = +0 beyond K
+      double av[4], bv[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int kx = kk + 4 * e + s, kc = min(kx, K - 1);
+        const double va = ap[kc * lda], vb = bp[kc];
+        av[e] = kx < K ? va : -0.0; bv[e] = kx < K ? vb : 0.0;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) if (kk + 4 * e < K) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[e], av[e], acc, 0, 0, 0);
+    }
+  }
+  static_for<4>([&](auto r) {
+    const int jc = j0 + s + 4 * r.value;
+    if (mv && jc < g.n) ((GM double*)c)[(long long)jc * g.ldc + i] = acc[r.value];
+  });
+}
+
+}  // namespace group_tile
+}  // namespace xamd

@@ -1,0 +1,69 @@
+// gemm_segments_kernels.hip -- libxsmm_hip_gemm_batch_reduce_segments: ADDRESS batch-reduce products with a reduce count of their own per C block, one launch.
+//
+// Segment s sums the products a_list[r] * b_list[r], seg_ptr[s] <= r < seg_ptr[s + 1], into c_list[s] [ref: src/generator_gemm_reference_impl.c:490-498: the
+// count and the two pointer lists are read per call].  A work item is (segment, C tile): item = segment * tiles + tile.  Every wave owns one item at a time and
+// the waves grid-stride over the items in ascending order, as the grouped kernels do, so the segments a caller lists first start first.  The shape, the leading
+// dimensions, beta, the layout bits and the tile edge are the same for every item and travel by value in the kernel arguments (a GemmGroupDesc whose operand
+// and stride slots are unused): no table, nothing uploaded.  Per item a wave reads seg_ptr[s], seg_ptr[s + 1] and c_list[s], then walks the two lists; the
+// item index is wave-uniform, so all of these are scalar loads, and the pointer pair of product r + 1 is requested before product r's MFMAs are issued
+// (ListChain::fetch in gemm_group_tile.hpp).  A whole segment is ONE accumulator chain over (product, k) on one wave -- the reference's order; a long segment
+// is never split.  A segment of count 0 stores beta * C (beta = 0: +0; beta = 1: C's own bits).  No LDS, no barrier, no scratch; C leaves through vector stores.
+// Block pointers are only known to be element-aligned: 16- / 8-byte loads of B columns and 4-byte loads of VNNI A pairs are chosen per product by a
+// wave-uniform test of the pointer, the element-wise loads remain for every other product.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include "internal.hpp"
+#include "gemm_device.hpp"
+#include "bf16_cvt.hpp"
+#include "gemm_group_tile.hpp"
+
+namespace xamd {
+
+using namespace group_tile;
+
+// CLS: 0 f32, 1 bf16, 2 f64
+template <int CLS>
+__device__ __forceinline__ void segments_body(const GemmGroupDesc& g, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list,
+  void* const* c_list, unsigned long long total) {
+  const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned int lane = threadIdx.x & 63u;
+  const unsigned long long step = (unsigned long long)gridDim.x * 4u;
+  const unsigned int tiles = (unsigned int)(g.tiles_m * g.tiles_n);
+  for (unsigned long long item = (unsigned long long)blockIdx.x * 4u + wave; item < total; item += step) {
+    unsigned long long s = item; unsigned int t = 0;
+    if (tiles != 1) { s = item / tiles; t = (unsigned int)(item - s * tiles); }
+    const unsigned int tn = t / (unsigned int)g.tiles_m, tm = t - tn * (unsigned int)g.tiles_m;
+    const unsigned long long r0 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s]), r1 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s + 1]);
+    gptr c = (gptr)list_entry((const void*)c_list, s);
+    const ListChain ch{(const void*)(a_list + r0), (const void*)(b_list + r0), r1 - r0, g.a_vec4, g.b_vec16, g.b_vec8};
+    if constexpr (CLS == 2) tile_f64(g, ch, c, (int)tm * 16, (int)tn * 16, lane);
+    else if (g.tile == 32) {
+      if constexpr (CLS == 1) tile_bf16<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane); else tile_f32<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane);
+    } else {
+      if constexpr (CLS == 1) tile_bf16<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane); else tile_f32<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void gemm_segments_f32_kernel(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list,
+  const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { segments_body<0>(g, seg_ptr, a_list, b_list, c_list, total); }
+__global__ __launch_bounds__(256) void gemm_segments_bf16_kernel(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list,
+  const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { segments_body<1>(g, seg_ptr, a_list, b_list, c_list, total); }
+__global__ __launch_bounds__(256) void gemm_segments_f64_kernel(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list,
+  const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { segments_body<2>(g, seg_ptr, a_list, b_list, c_list, total); }
+
+const char* gemm_segments_kernel_name(int cls) { return cls == 2 ? "gemm_segments_f64_kernel" : (cls == 1 ? "gemm_segments_bf16_kernel" : "gemm_segments_f32_kernel"); }
+
+int launch_gemm_segments(const GemmGroupDesc& g, int cls, unsigned long long items, const unsigned long long* seg_ptr, const void* const* a_list,
+  const void* const* b_list, void* const* c_list, void* stream) {
+  if (items == 0) return 0;
+  // one wave per item up to 32 768 workgroups (16 rounds of the chip's resident waves); beyond that the waves grid-stride
+  const unsigned int grid = (unsigned int)std::min<unsigned long long>((items + 3) / 4, 32768ull);
+  hipStream_t st = (hipStream_t)stream;
+  if (cls == 2) hipLaunchKernelGGL(gemm_segments_f64_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
+  else if (cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
+  else hipLaunchKernelGGL(gemm_segments_f32_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
+  return (int)hipGetLastError();
+}
+
+}  // namespace xamd

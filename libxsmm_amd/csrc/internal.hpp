@@ -294,6 +294,11 @@ int launch_gemm_grouped(const GemmGroupDesc* table, int ngroups, unsigned long l
 constexpr int kGroupedInline = 24;                // tables of up to this many groups travel in the kernel arguments (launch_gemm_grouped_inline: host table)
 int launch_gemm_grouped_inline(const GemmGroupDesc* host_table, int ngroups, unsigned long long items, int bf16, void* stream);
 const char* gemm_grouped_kernel_name(int bf16);
+// gemm_segments_kernels.hip (libxsmm_hip_gemm_batch_reduce_segments): `g` carries the shape, leading dimensions, beta, layout bits, tile edge and what the leading
+// dimensions allow of the wider loads (a_vec4 / b_vec16 / b_vec8); its operand, stride and prefix slots are unused.  cls: 0 f32, 1 bf16, 2 f64.  The lists are device-accessible.
+int launch_gemm_segments(const GemmGroupDesc& g, int cls, unsigned long long items, const unsigned long long* seg_ptr, const void* const* a_list,
+  const void* const* b_list, void* const* c_list, void* stream);
+const char* gemm_segments_kernel_name(int cls);
 int launch_spmm(const SpmmArgs& args, void* stream, const char** kernel_name);
 int launch_bcsc(const BcscArgs& args, void* stream, const char** kernel_name);
 // Automatic streaming decision (libxsmm_hip_set_streaming_hint(0)): a launch whose own operands exceed the Infinity Cache streams -- and so does a launch whose operands

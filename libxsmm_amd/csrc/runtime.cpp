@@ -2325,6 +2325,62 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* gr
     if (c->kind == K_GEMM) run_gemm(c, &grp.param, b); else run_spmm(c, &grp.param, b);
   }
 }
+// ---- segments (libxsmm_hip_gemm_batch_reduce_segments): ADDRESS batch-reduce with a count per C block, one launch -------------------------------------
+// The count is the one argument of a BRGEMM call that the reference re-reads on every call [ref: gemm ref :490-492]; here it is seg_ptr[s + 1] - seg_ptr[s].
+// Nothing is staged or uploaded: the four arrays are read on the device as they are, the shape travels in the kernel arguments, so the call can be captured.
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
+  const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list) {
+  static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments";
+  if (nsegments == 0) return;
+  if (!param || !seg_ptr || !a_list || !b_list || !c_list) {
+    set_error(-2, "%s: %s is NULL but nsegments = %zu", fn, !param ? "param" : (!seg_ptr ? "seg_ptr" : (!a_list ? "a_list" : (!b_list ? "b_list" : "c_list"))), nsegments); return;
+  }
+  KernelCtx* k = ctx_from_handle((const void*)kernel);
+  if (!k) { set_error(-3, "%s: unknown kernel handle", fn); return; }
+  if (k->kind != K_GEMM) { set_error(-3, "%s: handle is not a BRGEMM kernel (TPP, equation and sparse handles are not taken)", fn); return; }
+  const libxsmm_gemm_descriptor& d = k->g;
+  if (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI) { set_error(-3, "%s: ext handles are not taken", fn); return; }
+  if (!(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS)) { set_error(-3, "%s: handle is not an ADDRESS batch-reduce kernel (libxsmm_dispatch_brgemm with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS)", fn); return; }
+  const bool f32 = d.a_type == LIBXSMM_DATATYPE_F32 && d.b_type == LIBXSMM_DATATYPE_F32 && d.c_type == LIBXSMM_DATATYPE_F32;
+  const bool f64 = d.a_type == LIBXSMM_DATATYPE_F64 && d.b_type == LIBXSMM_DATATYPE_F64 && d.c_type == LIBXSMM_DATATYPE_F64;
+  const bool bf16 = d.a_type == LIBXSMM_DATATYPE_BF16 && d.b_type == LIBXSMM_DATATYPE_BF16 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF16);
+  if (!f32 && !f64 && !bf16) {
+    set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return;
+  }
+  const unsigned int f = effective_gemm_flags(d);
+  if (f & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return; }
+  if (f & (LIBXSMM_GEMM_FLAG_VNNI_B | LIBXSMM_GEMM_FLAG_VNNI_C)) { set_error(-3, "%s: VNNI layouts of B and C are not taken (A flat or VNNI-2, B and C flat)", fn); return; }
+  const unsigned int allowed = LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_ALIGN_A | LIBXSMM_GEMM_FLAG_ALIGN_C_NTS_HINT | LIBXSMM_GEMM_FLAG_NO_RESET_TILECONFIG |
+    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS;
+  if (f & ~allowed) { set_error(-3, "%s: flags 0x%x are not taken (beta, VNNI_A and the hints only)", fn, f & ~allowed); return; }
+  // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers): the grouped kernels' bound
+  const unsigned long long lim = 1ull << 31;
+  if ((unsigned long long)d.lda * (d.k + 1) >= lim || (unsigned long long)d.ldb * d.n >= lim || (unsigned long long)d.ldc * d.n >= lim) {
+    set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return;
+  }
+  const int cls = f64 ? 2 : (bf16 ? 1 : 0);
+  const int tile = (f64 || (d.m <= 16 && d.n <= 16)) ? 16 : 32;
+  GemmGroupDesc g;
+  std::memset(&g, 0, sizeof(g));
+  g.m = (int)d.m; g.n = (int)d.n; g.k = (int)d.k; g.lda = (int)d.lda; g.ldb = (int)d.ldb; g.ldc = (int)d.ldc;
+  g.tile = tile; g.tiles_m = (int)((d.m + tile - 1) / tile); g.tiles_n = (int)((d.n + tile - 1) / tile);
+  g.beta1 = (f & LIBXSMM_GEMM_FLAG_BETA_0) ? 0 : 1;
+  g.vnni_a = (bf16 && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
+  g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
+  // what the leading dimension allows of the wider loads; the block pointers are tested per product on the device
+  const unsigned long long colb = (unsigned long long)d.ldb * (bf16 ? 2 : (f64 ? 8 : 4));
+  g.a_vec4 = bf16 ? 1 : 0; g.b_vec16 = (colb & 15) == 0 ? 1 : 0; g.b_vec8 = (colb & 7) == 0 ? 1 : 0;
+  const unsigned long long tiles = (unsigned long long)g.tiles_m * (unsigned long long)g.tiles_n;
+  if (tiles != 0 && (unsigned long long)nsegments > ~0ull / tiles - 4) { set_error(-3, "%s: nsegments x C tiles overflows 64 bits", fn); return; }
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  if (tiles == 0) return;                               // m or n is 0: no C
+  const char* kname = gemm_segments_kernel_name(cls);
+  const int err = launch_gemm_segments(g, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream);
+  k->kname_batched = kname;
+  finish_launch(err, kname);
+}
 // ---- multi-device launch from ONE host thread (the reference's scale-out axis is the caller's loop,
 // samples/xgemm/gemm_kernel.c:4063-4066) --------------------------------------------------------------------------------------------------------
 // Every shard has a context of its own on the calling thread -- device, a non-blocking stream there, staging scratch, partial-result workspaces -- that is
