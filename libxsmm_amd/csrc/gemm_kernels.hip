@@ -97,11 +97,20 @@ __device__ __forceinline__ void generic_epilogue(const GemmArgs& p, const BatchP
     GM unsigned short* c = (GM unsigned short*)q.c;
     c[(long long)(j / 2) * p.ldc * 2 + (long long)i * 2 + (j % 2)] = p.c_type == LIBXSMM_DATATYPE_F16 ? __builtin_bit_cast(unsigned short, (_Float16)y) : f32_to_bf16_rne(y);
     if ((p.n & 1) && j == p.n - 1) c[(long long)(j / 2) * p.ldc * 2 + (long long)i * 2 + 1] = 0;
+    // the reference's re-layout zero-fills the whole ldc x n image before it moves the m rows [mateltwise ref :543-545]: rows m .. ldc - 1 come back as zeros
+    if (i == p.m - 1) for (int ii = p.m; ii < p.ldc; ++ii) {
+      c[(long long)(j / 2) * p.ldc * 2 + (long long)ii * 2 + (j % 2)] = 0;
+      if ((p.n & 1) && j == p.n - 1) c[(long long)(j / 2) * p.ldc * 2 + (long long)ii * 2 + 1] = 0;
+    }
   } else if (p.vnni_c && (p.c_type == LIBXSMM_DATATYPE_BF8 || p.c_type == LIBXSMM_DATATYPE_HF8)) {
     // 8-bit results: NORM -> VNNI4 [ref: gemm ref :2806, mateltwise ref :737-759]; the pad columns up to a multiple of four are zero-filled
     GM unsigned char* c = (GM unsigned char*)q.c;
     c[(long long)(j / 4) * p.ldc * 4 + (long long)i * 4 + (j % 4)] = p.c_type == LIBXSMM_DATATYPE_BF8 ? lowp::f16_to_bf8_rne(lowp::f32_to_f16(y)) : lowp::f16_to_hf8_rne(lowp::f32_to_f16(y));
     if (j == p.n - 1) for (int jj = p.n; (jj & 3) != 0; ++jj) c[(long long)(jj / 4) * p.ldc * 4 + (long long)i * 4 + (jj % 4)] = 0;
+    if (i == p.m - 1) for (int ii = p.m; ii < p.ldc; ++ii) {       // rows m .. ldc - 1 of the image: zeros, like the reference's re-layout [mateltwise ref :748-750]
+      c[(long long)(j / 4) * p.ldc * 4 + (long long)ii * 4 + (j % 4)] = 0;
+      if (j == p.n - 1) for (int jj = p.n; (jj & 3) != 0; ++jj) c[(long long)(jj / 4) * p.ldc * 4 + (long long)ii * 4 + (jj % 4)] = 0;
+    }
   } else if (p.c_type == LIBXSMM_DATATYPE_F32) {
     ((GM float*)q.c)[(long long)j * p.ldc + i] = y;
   } else if (p.c_type == LIBXSMM_DATATYPE_F16) {        // (the reduce pass of a k-sliced GEMM with IEEE-half C: round 3; fused IEEE-half GEMMs: round 6)
@@ -2137,6 +2146,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_forms_kernel(GemmArgs p) {
     for (int g2 = 0; g2 < 8; ++g2) {
       const unsigned int j = (unsigned int)job.j0 + (unsigned int)jl_of(2 * g2, (int)h);
       st_stream(c32 + (unsigned long long)(j >> 1) * (unsigned int)p.ldc + (unsigned int)tc.i, bf16_pk_exact(acc[2 * g2], acc[2 * g2 + 1]));
+      // rows m .. ldc - 1 of the image come back as zeros (the reference's re-layout zero-fills ldc x n first): the waves of the last tile row write them
+      if (job.i0 + 32 == p.m) for (unsigned int ii = (unsigned int)p.m + li; ii < (unsigned int)p.ldc; ii += 32u) st_stream(c32 + (unsigned long long)(j >> 1) * (unsigned int)p.ldc + ii, 0u);
     }
   } else tile_store<true, false>(acc, p, q, tc);
 }

@@ -677,7 +677,9 @@ void run_gemm(KernelCtx* k, const void* param, const BatchSpec& b) {
                                                              type == LIBXSMM_DATATYPE_I1X8 ? elems / 8 : type == LIBXSMM_DATATYPE_I2X4 ? elems / 4 : elems * (size_t)typesize(type); };
     const size_t ea = bytes_of(d.a_type, (size_t)a.lda * (size_t)(ta ? a.m : a.k));
     const size_t eb = bytes_of(d.b_type, (size_t)a.ldb * (size_t)((tb || mxmx) ? a.k : a.n));
-    const size_t ec = bytes_of(d.c_type, (size_t)a.ldc * (size_t)(a.n + (a.vnni_c ? (a.n & 1) : 0)));
+    // VNNI_C: the image holds the pad columns up to the VNNI factor of C's type (2 for 16-bit, 4 for 8-bit results)
+    const int vfc = a.vnni_c ? (typesize(d.c_type) == 1 ? 4 : 2) : 1;
+    const size_t ec = bytes_of(d.c_type, (size_t)a.ldc * (size_t)((a.n + vfc - 1) / vfc * vfc));
     const size_t span = (a.br_mode == 3) ? (size_t)(a.br_count - 1) : 0;
     if (a.br_mode != 3 || (a.br_stride_a >= 0 && a.br_stride_b >= 0)) {
       a.a = (const char*)stage(a.a, span * (size_t)a.br_stride_a + ea, true, false);
@@ -1273,7 +1275,8 @@ bool coalesce_try(KernelCtx* k, const void* param) {
   const bool ta = (d.flags & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (d.flags & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
   const size_t ea = (size_t)(brc - 1) * (size_t)(strided ? d.br_stride_a : 0) + (size_t)d.lda * (size_t)(ta ? d.m : d.k) * (size_t)typesize(d.a_type);
   const size_t eb = (size_t)(brc - 1) * (size_t)(strided ? d.br_stride_b : 0) + (size_t)d.ldb * (size_t)(tb ? d.k : d.n) * (size_t)typesize(d.b_type);
-  const size_t ec = (size_t)d.ldc * (size_t)(d.n + ((d.flags & LIBXSMM_GEMM_FLAG_VNNI_C) ? (d.n & 1) : 0)) * (size_t)typesize(d.c_type);
+  const int vfc = (d.flags & LIBXSMM_GEMM_FLAG_VNNI_C) ? (typesize(d.c_type) == 1 ? 4 : 2) : 1;      // pad columns up to the VNNI factor of C's type
+  const size_t ec = (size_t)d.ldc * (size_t)((d.n + vfc - 1) / vfc * vfc) * (size_t)typesize(d.c_type);
   const uintptr_t pa = (uintptr_t)p->a.primary, pb = (uintptr_t)p->b.primary, pc = (uintptr_t)p->c.primary;
   if (!q.a.empty()) {
     // read-after-write: this call's A / B against the queued C ranges; write-after-write / write-after-read: its C against the queued C and A / B ranges

@@ -335,7 +335,7 @@ class GemmCase:
         return out, (mask.cpu().numpy() if mask is not None else None), handle
 
     def valid_region(self, Cbuf: np.ndarray) -> np.ndarray:
-        """The m x n part of every batch element's C (padding rows between ldc and m are don't-care)."""
+        """The m x n part of every batch element's C (plain layout; the rows between m and ldc belong to the caller: tests/gemm_ld_helpers.py checks them)."""
         c = Cbuf.reshape(self.batch, -1)[:, : self.ldc * self.n].reshape(self.batch, self.n, self.ldc)
         return c[:, :, : self.m]
 

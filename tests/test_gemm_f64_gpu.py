@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gemm_ld_helpers import assert_dense
 from helpers import GemmCase, TOL_F64, normf_rel
 from libxsmm_amd import capi
 from libxsmm_amd.capi import DT, GEMM_FLAG as F
@@ -31,6 +32,7 @@ def _run(case, batched=True, expect=None):
     pad_ref = ref.reshape(case.batch, -1)[:, : case.ldc * case.n].reshape(case.batch, case.n, case.ldc)[:, :, case.m:]
     pad_got = got.reshape(case.batch, -1)[:, : case.ldc * case.n].reshape(case.batch, case.n, case.ldc)[:, :, case.m:]
     assert np.array_equal(pad_ref, pad_got), f"{name}: wrote into the padding of C"
+    assert_dense(case, got, ref)
     return name
 
 

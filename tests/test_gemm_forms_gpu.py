@@ -4,6 +4,7 @@ oracle's restatement of the reference loop within the reference driver's own bf1
 import numpy as np
 import pytest
 
+from gemm_ld_helpers import assert_dense
 from helpers import GemmCase, TOL_BF16, TOL_F32, normf_rel
 from libxsmm_amd import capi
 from libxsmm_amd.capi import DT, GEMM_FLAG as F
@@ -36,6 +37,7 @@ def test_every_operand_form_on_the_matrix_cores(af, bf, kw):
     assert api.hip_kernel_name(handle, 1).decode() == "gemm_bf16_forms_kernel"
     err = normf_rel(case.valid_region(ref), case.valid_region(got), case.c_type)
     assert err < (TOL_BF16 if case.c_type == DT.BF16 else TOL_F32), err
+    assert_dense(case, got, ref, got_mask=gmask)
 
 
 @pytest.mark.parametrize("af,bf", [("vnni", "flat"), ("flat", "trans"), ("trans", "tvnni")])
@@ -48,6 +50,7 @@ def test_c_in_vnni2(af, bf):
     # the VNNI-2 image is a permutation of C: compare it as it lies (bf16 -> f64), norm-wise
     err = normf_rel(ref, got, DT.BF16)
     assert err < TOL_BF16, err
+    assert_dense(case, got, ref)
 
 
 def test_shapes_and_alignments_outside_the_plan_stay_exact():
@@ -58,3 +61,4 @@ def test_shapes_and_alignments_outside_the_plan_stay_exact():
         ref, _ = case.run_oracle()
         assert api.hip_kernel_name(handle, 1).decode() == "gemm_generic_kernel"
         assert np.array_equal(case.valid_region(ref), case.valid_region(got))
+        assert_dense(case, got, ref)

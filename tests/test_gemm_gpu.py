@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gemm_ld_helpers import assert_dense
 from helpers import GemmCase, TOL_BF16, TOL_F32, TOL_F64, as_float, normf_rel
 from libxsmm_amd import capi
 from libxsmm_amd.capi import DT, GEMM_FLAG
@@ -55,6 +56,8 @@ def _check(case, batched=True, expect_kernel=None):
         decided = np.abs(pre) > (1e-5 if case.c_type in (DT.F32, DT.F64) else 1e-2)
         assert decided.mean() > 0.5
         assert np.array_equal(rb[decided], gb[decided])
+    # per problem / per element, the bytes of C outside m x n, and the mask bits decided by each element's own bound (tests/gemm_ld_helpers.py)
+    assert_dense(case, got, ref, got_mask=gmask)
     return name
 
 
@@ -235,6 +238,7 @@ def test_f16_gemm_matches_oracle(kw):
     name = api.hip_kernel_name(handle, 1).decode()
     err = normf_rel(case.valid_region(ref), case.valid_region(got), case.c_type)
     assert err < (1e-3 if case.c_type == DT.F16 else TOL_F32), f"{name}: normf_rel={err}"
+    assert_dense(case, got, ref)
     if "generic" in name:
         assert np.array_equal(case.valid_region(ref), case.valid_region(got)), "generic kernel must be bit-identical to the oracle"
     elif kw.get("flags", 0) == F.VNNI_A:
@@ -266,6 +270,7 @@ def test_f16_takes_the_bf16_fast_paths(kw, kernel):
     assert name == kernel, name
     err = normf_rel(case.valid_region(ref), case.valid_region(got), case.c_type)
     assert err < (1e-3 if case.c_type == DT.F16 else TOL_F32), f"{name}: normf_rel={err}"
+    assert_dense(case, got, ref)
 
 
 def test_f64_gemm_runs_on_the_f64_matrix_cores():

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from gemm_ld_helpers import assert_dense
 from helpers import GemmCase, TOL_F32, normf_rel
 from libxsmm_amd import capi
 from libxsmm_amd.capi import DT, GEMM_FLAG
@@ -33,6 +34,7 @@ def _run(case, expect="gemm_f32_ragged_kernel"):
         pad = np.ones((case.n, case.ldc), dtype=bool); pad[:, :case.m] = False
         c0 = case.C0.reshape(case.batch, case.n, case.ldc)
         assert np.array_equal(full_got.reshape(case.batch, case.n, case.ldc)[:, pad], c0[:, pad])
+    assert_dense(case, got, ref)
     return name
 
 

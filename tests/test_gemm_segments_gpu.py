@@ -89,7 +89,7 @@ class Pool:
 class Segments:
     """One segments call: pools of A and B blocks, one C block per segment, the CSR-style lists -- on the host for the oracle and on the device."""
 
-    def __init__(self, api, m, n, k, counts=COUNTS, a_type=DT.F32, c_type=None, flags=0, beta=0, lda=None, ldb=None, ldc=None, seed=0, exact=False, npool=9):
+    def __init__(self, api, m, n, k, counts=COUNTS, a_type=DT.F32, c_type=None, flags=0, beta=0, lda=None, ldb=None, ldc=None, seed=0, exact=False, npool=9, prepare=None):
         self.api = api
         self.case = case = GemmCase(m, n, k, a_type=a_type, c_type=c_type, lda=lda, ldb=ldb, ldc=ldc, flags=flags, beta=beta,
                                     br_type=capi.BR_ADDRESS, br_count=1, batch=1, seed=seed)
@@ -106,6 +106,8 @@ class Segments:
         r_of = np.arange(total) - self.seg_ptr[seg_of].astype(np.int64)
         self.ai = (seg_of * 3 + r_of) % npool                                     # A blocks are shared across segments ...
         self.bi = np.where(seg_of % 2 == 0, seg_of % npool, (seg_of + r_of) % npool)   # ... and even segments use ONE B for all their products
+        if prepare is not None:              # the host pools before they are uploaded (tests/test_gemm_ld_gpu.py poisons the gaps of every block)
+            prepare(self)
         self.dA, self.dB = self.A.upload(), self.B.upload()
         self.d_seg = _up(self.seg_ptr)
         self.d_la, self.d_lb = _up(self.A.dev_ptrs(self.dA, self.ai)), _up(self.B.dev_ptrs(self.dB, self.bi))
