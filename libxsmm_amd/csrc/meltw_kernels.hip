@@ -31,6 +31,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float mw_bf2f(unsigned short x) { return __uint_as_float((unsigned int)x << 16); }
+// bf16 -> f32 as the reference's element-wise loops load it: a denormal becomes a signed zero (DAZ) [ref: src/libxsmm_math.c:587-597, mateltwise ref :282]
+// (the block quantisers read the bits as they are: mw_bf2f)
+__device__ __forceinline__ float mw_bf2f_daz(unsigned short x) { return __uint_as_float((unsigned int)(((x & 0x7f80u) == 0u) ? (x & 0x8000u) : x) << 16); }
 __device__ __forceinline__ unsigned short mw_f2bf(float f) {
   unsigned int u = __float_as_uint(f);
   if ((u & 0x7f800000u) == 0u) u &= 0x80000000u;
@@ -52,6 +55,10 @@ __device__ __forceinline__ float mw_load(gcptr p, long long idx, int type) {
     case LIBXSMM_DATATYPE_HF8: return lowp::hf8_to_f32(((GM const unsigned char*)p)[idx]);
     default: return mw_bf2f(((GM const unsigned short*)p)[idx]);
   }
+}
+// ... of the unary / binary / ternary element-wise kernels
+__device__ __forceinline__ float mw_load_ew(gcptr p, long long idx, int type) {
+  return type == LIBXSMM_DATATYPE_BF16 ? mw_bf2f_daz(((GM const unsigned short*)p)[idx]) : mw_load(p, idx, type);
 }
 __device__ __forceinline__ void mw_store(gptr p, long long idx, int type, float v) {
   switch (type) {
@@ -184,18 +191,18 @@ __global__ __launch_bounds__(256) void meltw_unary_kernel(MeltwArgs p) {
   }
   switch (p.type) {
     case LIBXSMM_MELTW_TYPE_UNARY_RELU: case LIBXSMM_MELTW_TYPE_UNARY_LEAKY_RELU: case LIBXSMM_MELTW_TYPE_UNARY_ELU: {
-      const float x = e.valid ? mw_load(in, bc_index(bc, i, j, p.ldi), p.in0_type) : 0.0f;
+      const float x = e.valid ? mw_load_ew(in, bc_index(bc, i, j, p.ldi), p.in0_type) : 0.0f;
       if (e.valid) mw_store(out, i + (long long)j * p.ldo, p.out_type, unary_math(p.type, x, p.scalar_f32));
       if (bitm) put_bits((GM unsigned char*)p.aux_out + (long long)e.bidx * p.bs_aux, i, j, ((p.ldo + 15) / 16) * 16, e.valid, !(x <= 0.0f));
       return;
     }
     case LIBXSMM_MELTW_TYPE_UNARY_RELU_INV: case LIBXSMM_MELTW_TYPE_UNARY_LEAKY_RELU_INV: case LIBXSMM_MELTW_TYPE_UNARY_ELU_INV: {
       if (!e.valid) return;
-      const float x = mw_load(in, bc_index(bc, i, j, p.ldi), p.in0_type);
+      const float x = mw_load_ew(in, bc_index(bc, i, j, p.ldi), p.in0_type);
       gcptr aux = (gcptr)p.aux_in + (long long)e.bidx * p.bs_aux;
       float y;
       if (p.type == LIBXSMM_MELTW_TYPE_UNARY_ELU_INV) {
-        const float fwd = mw_load(aux, bc_index(bc, i, j, p.ldi), p.in0_type);
+        const float fwd = mw_load_ew(aux, bc_index(bc, i, j, p.ldi), p.in0_type);
         y = (fwd > 0.0f) ? x : x * (fwd + p.scalar_f32);
       } else {
         const int bit = get_bit((GM const unsigned char*)aux, i, j, ((p.ldi + 15) / 16) * 16);
@@ -227,7 +234,7 @@ __global__ __launch_bounds__(256) void meltw_unary_kernel(MeltwArgs p) {
     }
     case LIBXSMM_MELTW_TYPE_UNARY_DUMP: {                       // identity that also lands in out.secondary, same ldo and type [ref: :2478-2494]
       if (!e.valid) return;
-      const float x = mw_load(in, bc_index(bc, i, j, p.ldi), p.in0_type);
+      const float x = mw_load_ew(in, bc_index(bc, i, j, p.ldi), p.in0_type);
       mw_store(out, i + (long long)j * p.ldo, p.out_type, x);
       mw_store((gptr)p.aux_out + (long long)e.bidx * p.bs_aux, i + (long long)j * p.ldo, p.out_type, x);
       return;
@@ -260,15 +267,13 @@ __global__ __launch_bounds__(256) void meltw_unary_kernel(MeltwArgs p) {
     default: break;
   }
   if (!e.valid) return;
-  // pure copies / zero fill of same-width types stay bit-exact (no float round trip)
-  if (p.in0_type == p.out_type && (p.type == LIBXSMM_MELTW_TYPE_UNARY_IDENTITY || p.type == LIBXSMM_MELTW_TYPE_UNARY_REPLICATE_COL_VAR)) {
-    const int sz = mw_size(p.in0_type);
-    if (sz == 4) ((GM unsigned int*)out)[i + (long long)j * p.ldo] = ((GM const unsigned int*)in)[bc_index(bc, i, j, p.ldi)];
-    else if (sz == 2) ((GM unsigned short*)out)[i + (long long)j * p.ldo] = ((GM const unsigned short*)in)[bc_index(bc, i, j, p.ldi)];
-    else ((GM unsigned char*)out)[i + (long long)j * p.ldo] = ((GM const unsigned char*)in)[bc_index(bc, i, j, p.ldi)];
+  // f32 copies move the bits.  The narrower types take the float round trip below like every other operation: the reference's IDENTITY loads to f32 and
+  // stores with its rounding, which flushes a bf16 denormal to zero and quiets a signalling NaN [ref: :2483-2485] -- and so do the two vector kernels
+  if (p.in0_type == p.out_type && p.in0_type == LIBXSMM_DATATYPE_F32 && (p.type == LIBXSMM_MELTW_TYPE_UNARY_IDENTITY || p.type == LIBXSMM_MELTW_TYPE_UNARY_REPLICATE_COL_VAR)) {
+    ((GM unsigned int*)out)[i + (long long)j * p.ldo] = ((GM const unsigned int*)in)[bc_index(bc, i, j, p.ldi)];
     return;
   }
-  const float x = mw_load(in, bc_index(bc, i, j, p.ldi), p.in0_type);
+  const float x = mw_load_ew(in, bc_index(bc, i, j, p.ldi), p.in0_type);
   mw_store(out, i + (long long)j * p.ldo, p.out_type, unary_math(p.type, x, p.scalar_f32));
 }
 
@@ -286,7 +291,7 @@ __global__ __launch_bounds__(256) void meltw_unary_vec4_kernel(MeltwArgs p) {
   gcptr in = (gcptr)p.in0 + (long long)bidx * p.bs_in0;
   gptr out = (gptr)p.out + (long long)bidx * p.bs_out;
   float x[4];
-  if (BF16) { const u16x4 v = *(GM const u16x4*)((GM const unsigned short*)in + i + (long long)j * p.ldi); for (int e = 0; e < 4; ++e) x[e] = mw_bf2f(v[e]); }
+  if (BF16) { const u16x4 v = *(GM const u16x4*)((GM const unsigned short*)in + i + (long long)j * p.ldi); for (int e = 0; e < 4; ++e) x[e] = mw_bf2f_daz(v[e]); }
   else { const f32x4 v = *(GM const f32x4*)((GM const float*)in + i + (long long)j * p.ldi); for (int e = 0; e < 4; ++e) x[e] = v[e]; }
   if (BF16) { u16x4 o; for (int e = 0; e < 4; ++e) o[e] = mw_f2bf(unary_math(p.type, x[e], p.scalar_f32)); *(GM u16x4*)((GM unsigned short*)out + i + (long long)j * p.ldo) = o; }
   else { f32x4 o; for (int e = 0; e < 4; ++e) o[e] = unary_math(p.type, x[e], p.scalar_f32); *(GM f32x4*)((GM float*)out + i + (long long)j * p.ldo) = o; }
@@ -315,7 +320,7 @@ template <bool NT, typename V> __device__ __forceinline__ void st_pol(GM V* p, V
 template <bool NT = false, int E = 8>      // E = 4: all operands f32, ONE 16-byte access per lane (a wave covers 1 KiB without gaps)
 __device__ __forceinline__ void ew8_load(float (&x)[E], gcptr base, int type, int kind, long long i, long long j, long long ld) {
   if (kind == BC_ROW || kind == BC_SCALAR) {
-    const float v = mw_load(base, kind == BC_ROW ? j * ld : 0, type);
+    const float v = mw_load_ew(base, kind == BC_ROW ? j * ld : 0, type);
 #pragma unroll
     for (int e = 0; e < E; ++e) x[e] = v;
     return;
@@ -333,7 +338,7 @@ __device__ __forceinline__ void ew8_load(float (&x)[E], gcptr base, int type, in
   } else {
     const u32x4e v = ld_pol<NT>((GM const u32x4e*)((GM const unsigned short*)base + idx));
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { x[2 * e] = __uint_as_float(v[e] << 16); x[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u); }
+    for (int e = 0; e < 4; ++e) { x[2 * e] = mw_daz(__uint_as_float(v[e] << 16)); x[2 * e + 1] = mw_daz(__uint_as_float(v[e] & 0xffff0000u)); }      // DAZ, as mw_bf2f_daz
   }
 }
 template <bool NT = false, int E = 8>
@@ -477,13 +482,13 @@ __global__ __launch_bounds__(256) void meltw_binary_kernel(MeltwArgs p) {
     return;
   }
   float a = 0.0f, b = 0.0f;
-  if (e.valid) { a = mw_load(in0, bc_index(bc0, i, j, p.ldi), p.in0_type); b = mw_load(in1, bc_index(bc1, i, j, p.ldi1), p.in1_type); }
+  if (e.valid) { a = mw_load_ew(in0, bc_index(bc0, i, j, p.ldi), p.in0_type); b = mw_load_ew(in1, bc_index(bc1, i, j, p.ldi1), p.in1_type); }
   if (cmp) {   // result is a bit matrix, ld rounded up to 16 [ref: :2575-2584]
     put_bits((GM unsigned char*)out, i, j, ((p.ldo + 15) / 16) * 16, e.valid, binary_math(p.type, a, b, 0.0f) > 0.1f);
     return;
   }
   if (!e.valid) return;
-  const float prev = (p.type == LIBXSMM_MELTW_TYPE_BINARY_MULADD) ? mw_load(out, i + (long long)j * p.ldo, p.out_type) : 0.0f;
+  const float prev = (p.type == LIBXSMM_MELTW_TYPE_BINARY_MULADD) ? mw_load_ew(out, i + (long long)j * p.ldo, p.out_type) : 0.0f;
   mw_store(out, i + (long long)j * p.ldo, p.out_type, binary_math(p.type, a, b, prev));
 }
 
@@ -502,14 +507,14 @@ __global__ __launch_bounds__(256) void meltw_ternary_kernel(MeltwArgs p) {
       const double a = ((GM const double*)in0)[bc_index(bc0, i, j, p.ldi)], b = ((GM const double*)in1)[bc_index(bc1, i, j, p.ldi1)];
       ((GM double*)out)[i + (long long)j * p.ldo] = bit ? b : a;
     } else {
-      const float a = mw_load(in0, bc_index(bc0, i, j, p.ldi), p.in0_type), b = mw_load(in1, bc_index(bc1, i, j, p.ldi1), p.in1_type);
+      const float a = mw_load_ew(in0, bc_index(bc0, i, j, p.ldi), p.in0_type), b = mw_load_ew(in1, bc_index(bc1, i, j, p.ldi1), p.in1_type);
       mw_store(out, i + (long long)j * p.ldo, p.out_type, bit ? b : a);
     }
     return;
   }
-  const float a = mw_load(in0, bc_index(bc0, i, j, p.ldi), p.in0_type);
-  const float b = mw_load(in1, bc_index(bc1, i, j, p.ldi1), p.in1_type);
-  const float c = mw_load(in2, bc_index(bc2, i, j, p.ldi2), p.in2_type);
+  const float a = mw_load_ew(in0, bc_index(bc0, i, j, p.ldi), p.in0_type);
+  const float b = mw_load_ew(in1, bc_index(bc1, i, j, p.ldi1), p.in1_type);
+  const float c = mw_load_ew(in2, bc_index(bc2, i, j, p.ldi2), p.in2_type);
   const float prod = (p.type == LIBXSMM_MELTW_TYPE_TERNARY_MULADD) ? a * b : a * c;
   const float r = (p.type == LIBXSMM_MELTW_TYPE_TERNARY_MULADD) ? c + prod : b - prod;   // [ref: :2641-2655]
   mw_store(out, i + (long long)j * p.ldo, p.out_type, r);

@@ -65,7 +65,8 @@ static float half_bits_to_f32(unsigned short h) {
   else r.u = s | ((e + 112u) << 23) | (m << 13);
   return r.f;
 }
-float oracle_bf8_to_f32(unsigned char x) { return half_bits_to_f32((unsigned short)((unsigned short)x << 8)); }
+/* through the half conversion, which quiets a signalling NaN (0x7d / 0x7e / 0xfd / 0xfe keep their payload bit, the quiet bit is set) [ref: :546-551, :629-632] */
+float oracle_bf8_to_f32(unsigned char x) { return oracle_f16_to_f32((unsigned short)((unsigned short)x << 8)); }
 float oracle_hf8_to_f32(unsigned char in) {
   const unsigned int s = (unsigned int)(in & 0x80u) << 24, e = (in & 0x78u) >> 3;
   unsigned int m = in & 0x07u, e_norm = e + (127u - 7u);

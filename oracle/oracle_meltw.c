@@ -57,7 +57,11 @@ static long long elem_index(int kind, long long i, long long j, long long ld) { 
 }
 static float get_f32(const void* p, long long idx, int type) {                     /* [:274-297] */
   if (type == LIBXSMM_DATATYPE_F32) return ((const float*)p)[idx];
-  if (type == LIBXSMM_DATATYPE_BF16) return oracle_bf16_to_f32(((const unsigned short*)p)[idx]);
+  if (type == LIBXSMM_DATATYPE_BF16) {                                              /* a bf16 denormal is loaded as a signed zero (DAZ) [ref: src/libxsmm_math.c:587-597] */
+    unsigned short x = ((const unsigned short*)p)[idx];
+    if ((x & 0x7f80u) == 0) x &= 0x8000u;
+    return oracle_bf16_to_f32(x);
+  }
   if (type == LIBXSMM_DATATYPE_F16) return oracle_f16_to_f32(((const unsigned short*)p)[idx]);
   if (type == LIBXSMM_DATATYPE_BF8) return oracle_bf8_to_f32(((const unsigned char*)p)[idx]);
   if (type == LIBXSMM_DATATYPE_HF8) return oracle_hf8_to_f32(((const unsigned char*)p)[idx]);

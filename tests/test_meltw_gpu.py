@@ -11,7 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import NP_OF, normf_rel, rand_values
+from helpers import NP_OF, as_float, normf_rel, rand_values
+from meltw_ew_helpers import assert_approx
 from libxsmm_amd import capi
 from libxsmm_amd.capi import BINARY, BINARY_FLAG, DT, TERNARY, TERNARY_FLAG, UNARY, UNARY_FLAG
 from oracle import pyoracle
@@ -31,7 +32,7 @@ def _back(t, like):
 
 
 def run_unary(typ, m, n, ldi, ldo, in_dt, out_dt, flags=0, seed=0, batch=1, aux_in=None, aux_out_bytes=0, op_primary=None,
-              in_elems=None, out_elems=None, out_secondary_val=None, inp=None, in_tertiary_val=None):
+              in_elems=None, out_elems=None, out_secondary_val=None, inp=None, in_tertiary_val=None, kernel=None):
     api, orc = capi.load(), pyoracle.oracle()
     rng = np.random.default_rng(seed)
     in_elems = in_elems if in_elems is not None else ldi * max(n, 1)
@@ -77,6 +78,8 @@ def run_unary(typ, m, n, ldi, ldo, in_dt, out_dt, flags=0, seed=0, batch=1, aux_
     else:
         api.hip_meltw_unary_batch_strided(h, C.byref(p), batch, in_elems * in_sz, out_elems * out_sz, aux_out_bytes)
     api.hip_sync(); api.check()
+    if kernel is not None:
+        assert api.hip_kernel_name(h, 1 if batch > 1 else 0).decode() == kernel
     got = _back(dY, Y0)
     return ref, got, aux_ref, (d_aux_out.cpu().numpy() if d_aux_out is not None else None)
 
@@ -94,11 +97,15 @@ def test_unary_math(typ, in_dt, out_dt, m, n, ldi, ldo, batch):
     if typ in (UNARY.SQRT, UNARY.RECIPROCAL_SQRT, UNARY.RECIPROCAL):
         v = (rng.random(batch * ldi * n) + 0.25).astype(np.float32)
         inp = v if in_dt == DT.F32 else (v.view(np.uint32) >> 16).astype(np.uint16)
-    ref, got, _, _ = run_unary(typ, m, n, ldi, ldo, in_dt, out_dt, batch=batch, inp=inp)
-    if typ in EXACT_UNARY and typ not in (UNARY.SQRT, UNARY.RECIPROCAL):
+    if inp is None:
+        inp = rand_values(rng, batch * ldi * n, in_dt)
+    ref, got, _, _ = run_unary(typ, m, n, ldi, ldo, in_dt, out_dt, batch=batch, inp=inp, kernel="meltw_unary_kernel" if m % 4 else "meltw_ew8_kernel")
+    if typ in EXACT_UNARY or typ == UNARY.RECIPROCAL_SQRT:      # sqrtf and the division are correctly rounded on the device as in the reference (tests/test_meltw_ew_gpu.py)
         assert np.array_equal(ref, got)
     else:
         assert normf_rel(ref, got, out_dt) < (7e-3 if out_dt == DT.BF16 else 7e-4)
+        x, g = inp.reshape(batch, n, ldi)[:, :, :m], got.reshape(batch, n, ldo)[:, :, :m]
+        assert_approx(typ, as_float(x, in_dt), as_float(g, out_dt), out_dt)           # ... and every element inside the libm bound
 
 
 @pytest.mark.parametrize("flag", [UNARY_FLAG.BCAST_ROW, UNARY_FLAG.BCAST_COL, UNARY_FLAG.BCAST_SCALAR])
@@ -120,8 +127,10 @@ def test_relu_with_bitmask_and_inverse(dt):
     alpha = C.c_float(0.3)
     r3, g3, _, _ = run_unary(UNARY.LEAKY_RELU, m, n, ld, ld, dt, dt, op_primary=alpha)
     assert np.array_equal(r3, g3)
-    r4, g4, _, _ = run_unary(UNARY.ELU, m, n, ld, ld, dt, dt, op_primary=alpha)
+    x4 = rand_values(np.random.default_rng(14), ld * n, dt)
+    r4, g4, _, _ = run_unary(UNARY.ELU, m, n, ld, ld, dt, dt, op_primary=alpha, inp=x4)
     assert normf_rel(r4, g4, dt) < 7e-3
+    assert_approx(UNARY.ELU, as_float(x4.reshape(n, ld)[:, :m], dt), as_float(g4.reshape(n, ld)[:, :m], dt), dt, alpha=float(alpha.value))
 
 
 def test_f64_unary():
@@ -131,34 +140,38 @@ def test_f64_unary():
 
 
 TRANSFORMS = [
-    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F32, 37, 19, 40, 19), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.BF16, 64, 64, 64, 64),
-    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F64, 5, 70, 8, 71), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.I8, 33, 34, 33, 34),
-    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 32, 16, 32, 32), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 13, 8, 16, 14),
-    (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.BF16, 16, 8, 16, 16), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 20, 12, 24, 20),
-    (UNARY.TRANSFORM_VNNI2_TO_VNNI2T, DT.BF16, 16, 8, 8, 16), (UNARY.TRANSFORM_NORM_TO_VNNI2T, DT.BF16, 16, 6, 16, 6),
-    (UNARY.TRANSFORM_VNNI4_TO_VNNI4T, DT.I8, 16, 8, 8, 16), (UNARY.TRANSFORM_NORM_TO_VNNI4T, DT.BF16, 16, 6, 16, 6),
-    (UNARY.TRANSFORM_VNNI4_TO_NORM, DT.I8, 12, 8, 12, 12), (UNARY.TRANSFORM_VNNI4_TO_VNNI2, DT.I8, 12, 8, 12, 12),
-    (UNARY.TRANSFORM_PADN_MOD2, DT.BF16, 9, 5, 10, 12), (UNARY.TRANSFORM_PADM_MOD2, DT.BF16, 9, 6, 10, 12),
-    (UNARY.TRANSFORM_PADNM_MOD4, DT.I8, 9, 6, 10, 12),
+    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F32, 37, 19, 40, 19, "transpose_kernel"), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.BF16, 64, 64, 64, 64, "transpose_vec_kernel"),
+    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F64, 5, 70, 8, 71, "transpose_kernel"), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.I8, 33, 34, 33, 34, "transpose_kernel"),
+    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 32, 16, 32, 32, "vnni2_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 13, 8, 16, 14, "vnni2_pair_kernel"),
+    (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.BF16, 16, 8, 16, 16, "xform_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 20, 12, 24, 20, "vnni4_vec_kernel"),
+    (UNARY.TRANSFORM_VNNI2_TO_VNNI2T, DT.BF16, 16, 8, 8, 16, "xform_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI2T, DT.BF16, 16, 6, 16, 6, "xform_kernel"),
+    (UNARY.TRANSFORM_VNNI4_TO_VNNI4T, DT.I8, 16, 8, 8, 16, "xform_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI4T, DT.BF16, 16, 6, 16, 6, "xform_kernel"),
+    (UNARY.TRANSFORM_VNNI4_TO_NORM, DT.I8, 12, 8, 12, 12, "xform_kernel"), (UNARY.TRANSFORM_VNNI4_TO_VNNI2, DT.I8, 12, 8, 12, 12, "xform_kernel"),
+    (UNARY.TRANSFORM_PADN_MOD2, DT.BF16, 9, 5, 10, 12, "xform_kernel"), (UNARY.TRANSFORM_PADM_MOD2, DT.BF16, 9, 6, 10, 12, "xform_kernel"),
+    (UNARY.TRANSFORM_PADNM_MOD4, DT.I8, 9, 6, 10, 12, "xform_kernel"),
     # vector kernels (16-byte accesses): full and edge tiles, every payload width, odd n with zero-filled pad row
-    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F32, 128, 96, 128, 96), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F32, 68, 200, 72, 208),
-    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.BF16, 72, 40, 80, 48), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F64, 66, 10, 66, 12), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.I8, 80, 32, 96, 32),
-    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 64, 7, 64, 72), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 136, 130, 144, 136),
+    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F32, 128, 96, 128, 96, "transpose_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F32, 68, 200, 72, 208, "transpose_vec_kernel"),
+    (UNARY.TRANSFORM_NORM_TO_NORMT, DT.BF16, 72, 40, 80, 48, "transpose_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.F64, 66, 10, 66, 12, "transpose_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_NORMT, DT.I8, 80, 32, 96, 32, "transpose_vec_kernel"),
+    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 64, 7, 64, 72, "vnni2_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 136, 130, 144, 136, "vnni2_vec_kernel"),
     # any leading dimensions, four positions per thread (round 4): ldi even / odd (odd rows 4- / 2-byte aligned), ldo % 4 in 0..3 (16- / 8- / 4-byte stores, short last
     # thread of a row), m < ldo (zero-filled positions), odd n (zero-filled pad row)
-    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 70, 9, 74, 78), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 61, 10, 63, 67), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 33, 5, 36, 37),
-    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 100, 12, 100, 100), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 47, 6, 47, 50), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 18, 4, 19, 21),
+    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 70, 9, 74, 78, "vnni2_quad_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 61, 10, 63, 67, "vnni2_quad_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 33, 5, 36, 37, "vnni2_quad_kernel"),
+    (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 100, 12, 100, 100, "vnni2_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 47, 6, 47, 50, "vnni2_quad_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI2, DT.BF16, 18, 4, 19, 21, "vnni2_quad_kernel"),
     # NORM -> VNNI4 of 8-bit payloads, vector kernel: n a multiple of 4, n with 1 / 2 / 3 rows missing (zero-filled), ldo > m (zero-filled columns)
-    (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 64, 16, 64, 64), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 132, 13, 136, 140), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 16, 6, 16, 16),
-    (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.BF8, 256, 35, 256, 260), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.HF8, 20, 12, 24, 20),
+    (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 64, 16, 64, 64, "vnni4_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 132, 13, 136, 140, "vnni4_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.I8, 16, 6, 16, 16, "vnni4_vec_kernel"),
+    (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.BF8, 256, 35, 256, 260, "vnni4_vec_kernel"), (UNARY.TRANSFORM_NORM_TO_VNNI4, DT.HF8, 20, 12, 24, 20, "vnni4_vec_kernel"),
 ]
 
 
-@pytest.mark.parametrize("typ,dt,m,n,ldi,ldo", TRANSFORMS)
+TRANSFORM_KERNEL = {row[:6]: row[6] for row in TRANSFORMS}        # the kernel launch_meltw picks for each row (a batch of two)
+
+
+@pytest.mark.parametrize("typ,dt,m,n,ldi,ldo", [row[:6] for row in TRANSFORMS])
 def test_transforms_bit_exact(typ, dt, m, n, ldi, ldo):
+    kernel = TRANSFORM_KERNEL[(typ, dt, m, n, ldi, ldo)]
     # generous buffers: VNNI layouts interleave rows, padded variants write beyond n columns
     elems = 4 * max(ldi, ldo) * (max(m, n) + 8)
-    ref, got, _, _ = run_unary(typ, m, n, ldi, ldo, dt, dt, in_elems=elems, out_elems=elems, batch=2)
+    ref, got, _, _ = run_unary(typ, m, n, ldi, ldo, dt, dt, in_elems=elems, out_elems=elems, batch=2, kernel=kernel)
     assert np.array_equal(ref, got)
 
 
@@ -176,8 +189,11 @@ def test_gather_scatter_bit_exact(dt, mode, idx8):
         idx = rng.choice(big, size=m, replace=False).astype(idt)
     else:
         idx = rng.choice(big * big, size=m * n, replace=False).astype(idt)
+    # 16-byte columns, rows through LDS, four offsets per thread (4-byte indices); single bytes and 8-byte offsets one element per thread
+    kernel = ("gather_scatter_kernel" if dt == DT.I8 else "gather_cols_vec_kernel" if mode == UNARY_FLAG.GS_COLS else "gs_rows_lds_kernel" if mode == UNARY_FLAG.GS_ROWS
+              else "gather_scatter_kernel" if idx8 else "gs_offs_vec4_kernel")
     # gather: big source -> compact m x n ; scatter: compact -> big destination
-    ref, got, _, _ = run_unary(UNARY.GATHER, m, n, big, m, dt, dt, flags=flags, aux_in=idx, in_elems=big * big, out_elems=m * n)
+    ref, got, _, _ = run_unary(UNARY.GATHER, m, n, big, m, dt, dt, flags=flags, aux_in=idx, in_elems=big * big, out_elems=m * n, kernel=kernel)
     assert np.array_equal(ref, got)
     api, orc = capi.load(), pyoracle.oracle()
     X, Y0 = rand_values(rng, m * n, dt), rand_values(rng, big * big, dt)
@@ -190,6 +206,7 @@ def test_gather_scatter_bit_exact(dt, mode, idx8):
     dX, dY, dI = _dev(X), _dev(Y0.copy()), _dev(idx)
     p = capi.UnaryParam(); p.in_.primary, p.out.primary, p.out.secondary = dX.data_ptr(), dY.data_ptr(), dI.data_ptr()
     capi.Api.call(h, p); api.hip_sync(); api.check()
+    assert api.hip_kernel_name(h, 0).decode() == kernel
     assert np.array_equal(refs, _back(dY, Y0))
 
 
@@ -203,7 +220,7 @@ def test_row_gather_of_many_columns_bit_exact(dt, idx8, m, n, big):
     idt = np.uint64 if idx8 else np.uint32
     flags = UNARY_FLAG.GS_ROWS | (UNARY_FLAG.IDX_SIZE_8BYTES if idx8 else UNARY_FLAG.IDX_SIZE_4BYTES)
     idx = rng.choice(big, size=m, replace=(m > big)).astype(idt)
-    ref, got, _, _ = run_unary(UNARY.GATHER, m, n, big, m, dt, dt, flags=flags, aux_in=idx, in_elems=big * n, out_elems=m * n)
+    ref, got, _, _ = run_unary(UNARY.GATHER, m, n, big, m, dt, dt, flags=flags, aux_in=idx, in_elems=big * n, out_elems=m * n, kernel="gs_rows_lds_multi_kernel")
     assert np.array_equal(ref, got)
 
 
@@ -214,7 +231,7 @@ def test_reductions(typ, rows, in_dt):
     m, n, ldi = 75, 33, 80
     res = n if rows else m
     flags = UNARY_FLAG.REDUCE_ROWS if rows else UNARY_FLAG.REDUCE_COLS
-    ref, got, _, _ = run_unary(typ, m, n, ldi, res, in_dt, DT.F32, flags=flags, out_elems=2 * res, batch=2)
+    ref, got, _, _ = run_unary(typ, m, n, ldi, res, in_dt, DT.F32, flags=flags, out_elems=2 * res, batch=2, kernel="reduce_kernel")
     r, g = ref.reshape(2, -1), got.reshape(2, -1)
     used = 2 * res if typ == UNARY.REDUCE_X_X2_OP_ADD else res
     if typ in (UNARY.REDUCE_X_OP_MAX, UNARY.REDUCE_X_OP_MIN, UNARY.REDUCE_X_OP_ABSMAX):
@@ -286,7 +303,7 @@ def test_reductions_vector_kernel(typ, rows, in_dt, m, n, ldi):
     """m % 4 == 0 and aligned: reduce_vec_kernel (lane groups per column / 16 column slices per row group when n >= 256)."""
     res = n if rows else m
     flags = UNARY_FLAG.REDUCE_ROWS if rows else UNARY_FLAG.REDUCE_COLS
-    ref, got, _, _ = run_unary(typ, m, n, ldi, res, in_dt, DT.F32, flags=flags, out_elems=2 * res, batch=2)
+    ref, got, _, _ = run_unary(typ, m, n, ldi, res, in_dt, DT.F32, flags=flags, out_elems=2 * res, batch=2, kernel="reduce_vec_kernel")
     r, g = ref.reshape(2, -1), got.reshape(2, -1)
     used = 2 * res if typ == UNARY.REDUCE_X_X2_OP_ADD else res
     if typ in (UNARY.REDUCE_X_OP_MAX, UNARY.REDUCE_X_OP_ABSMAX):
@@ -300,7 +317,7 @@ def test_reductions_vector_kernel(typ, rows, in_dt, m, n, ldi):
 def test_column_reduction_of_one_big_matrix_two_pass(typ, m, n):
     """One matrix, few rows, thousands of columns: the columns are split over the grid and combined in a second pass."""
     api = capi.load()
-    ref, got, _, _ = run_unary(typ, m, n, m, m, DT.F32, DT.F32, flags=UNARY_FLAG.REDUCE_COLS, out_elems=2 * m, batch=1)
+    ref, got, _, _ = run_unary(typ, m, n, m, m, DT.F32, DT.F32, flags=UNARY_FLAG.REDUCE_COLS, out_elems=2 * m, batch=1, kernel="reduce_vec_kernel+combine")
     used = 2 * m if typ == UNARY.REDUCE_X_X2_OP_ADD else m
     if typ == UNARY.REDUCE_X_OP_MAX:
         assert np.array_equal(ref[:used], got[:used])
@@ -308,7 +325,7 @@ def test_column_reduction_of_one_big_matrix_two_pass(typ, m, n):
         assert normf_rel(ref[:used], got[:used], DT.F32) < 1e-5
 
 
-def run_binary(typ, m, n, ldi, ldi1, ldo, dts, flags=0, seed=0, batch=1, out_is_bits=False):
+def run_binary(typ, m, n, ldi, ldi1, ldo, dts, flags=0, seed=0, batch=1, out_is_bits=False, kernel=None):
     api, orc = capi.load(), pyoracle.oracle()
     in0_dt, in1_dt, out_dt = dts
     rng = np.random.default_rng(seed)
@@ -335,6 +352,8 @@ def run_binary(typ, m, n, ldi, ldi1, ldo, dts, flags=0, seed=0, batch=1, out_is_
     else:
         api.hip_meltw_binary_batch_strided(h, C.byref(p), batch, s0, s1, out_bytes)
     api.hip_sync(); api.check()
+    if kernel is not None:
+        assert api.hip_kernel_name(h, 1 if batch > 1 else 0).decode() == kernel
     return ref, _back(dY, Y0)
 
 
@@ -350,7 +369,7 @@ def test_binary_arith_bit_exact(typ, dts):
 def test_dot_product_to_scalar(dts, m, n, ld, batch):
     """BINARY_MUL_AND_REDUCE_TO_SCALAR_OP_ADD: the device folds 1024 partial sums pairwise, the reference adds serially -- equal to f32
     summation error (|terms| <= 1, so either order is within count * 2^-24 * count of the exact sum; the bound below is far inside that)"""
-    ref, got = run_binary(BINARY.MUL_AND_REDUCE_TO_SCALAR_OP_ADD, m, n, ld, ld, 1, dts, batch=batch)
+    ref, got = run_binary(BINARY.MUL_AND_REDUCE_TO_SCALAR_OP_ADD, m, n, ld, ld, 1, dts, batch=batch, kernel="mul_reduce_scalar_kernel")
     from helpers import as_float
     stride = n                                     # run_binary lays one (ldo = 1) x n output per batch element; element 0 is the result
     for b in range(batch):
@@ -395,7 +414,7 @@ def test_zip_unzip_roundtrip_bit_exact():
 @pytest.mark.parametrize("m,n,ld,batch", [(45, 13, 48, 1), (64, 64, 64, 3), (1, 1, 1, 1), (7, 300, 9, 2)])
 def test_reduce_to_scalar(in_dt, out_dt, m, n, ld, batch):
     """REDUCE_TO_SCALAR_OP_ADD: a tree sum on the device against the reference's serial one -- the bound of the reduction tests (f64: 1e-12)"""
-    ref, got, _, _ = run_unary(UNARY.REDUCE_TO_SCALAR_OP_ADD, m, n, ld, 1, in_dt, out_dt, batch=batch, out_elems=4, seed=51)
+    ref, got, _, _ = run_unary(UNARY.REDUCE_TO_SCALAR_OP_ADD, m, n, ld, 1, in_dt, out_dt, batch=batch, out_elems=4, seed=51, kernel="reduce_scalar_kernel")
     r, g = ref.reshape(batch, 4), got.reshape(batch, 4)
     assert np.array_equal(r[:, 1:], g[:, 1:])                      # only element 0 of each output is written
     if in_dt == DT.F64:
@@ -410,7 +429,7 @@ def test_reduce_to_scalar(in_dt, out_dt, m, n, ld, batch):
 @pytest.mark.parametrize("bc,bn,C_,N_,batch", [(16, 4, 64, 32, 1), (8, 8, 8, 8, 3), (32, 2, 96, 10, 1), (5, 3, 20, 9, 2), (64, 16, 1024, 256, 1)])
 def test_reduce_ncnc_format_bit_exact(in_dt, out_dt, bc, bn, C_, N_, batch):
     """REDUCE_X_OP_ADD_NCNC_FORMAT: one thread per channel adds in the reference's order -- bit-exact"""
-    ref, got, _, _ = run_unary(UNARY.REDUCE_X_OP_ADD_NCNC_FORMAT, bc, bn, C_, N_, in_dt, out_dt, batch=batch, in_elems=C_ * N_, out_elems=C_ + 3, seed=52)
+    ref, got, _, _ = run_unary(UNARY.REDUCE_X_OP_ADD_NCNC_FORMAT, bc, bn, C_, N_, in_dt, out_dt, batch=batch, in_elems=C_ * N_, out_elems=C_ + 3, seed=52, kernel="reduce_ncnc_kernel")
     assert np.array_equal(ref, got)
 
 
@@ -491,6 +510,7 @@ def test_dropout_bit_exact(dt, m, n, ld, batch, bitm):
     else:
         api.hip_meltw_unary_batch_strided(h, C.byref(p), batch, ld * n * es, ld * n * es, mask_bytes)
     api.hip_sync(); api.check()
+    assert api.hip_kernel_name(h, 1 if batch > 1 else 0).decode() == "dropout_kernel"
     valid = lambda y: y.reshape(batch * n, ld)[:, :m]
     assert np.array_equal(valid(ref), valid(_back(dY, Y0)))
     assert np.array_equal(st_ref, dS.cpu().numpy().view(np.uint32))
@@ -498,7 +518,7 @@ def test_dropout_bit_exact(dt, m, n, ld, batch, bitm):
         bits = lambda x: np.unpackbits(x.reshape(batch * n, -1), axis=1, bitorder="little")[:, :m]
         got_mask = dM.cpu().numpy()
         assert np.array_equal(bits(mask_ref), bits(got_mask))
-        refi, goti, _, _ = run_unary(UNARY.DROPOUT_INV, m, n, ld, ld, dt, dt, flags=flags, aux_in=mask_ref[:mask_bytes].copy(), op_primary=prob)
+        refi, goti, _, _ = run_unary(UNARY.DROPOUT_INV, m, n, ld, ld, dt, dt, flags=flags, aux_in=mask_ref[:mask_bytes].copy(), op_primary=prob, kernel="dropout_inv_kernel")
         assert np.array_equal(refi.reshape(n, ld)[:, :m], goti.reshape(n, ld)[:, :m])
 
 
@@ -702,8 +722,10 @@ LOWP_PAIRS = [(DT.F16, DT.F16), (DT.BF8, DT.BF8), (DT.HF8, DT.HF8), (DT.F32, DT.
 def test_unary_16_and_8_bit_floats(typ, in_dt, out_dt):
     """F16 / BF8 / HF8 operands of the TPPs (device conversions = libxsmm_amd/csrc/lowp.hpp, the code pinned against the reference on the
     host): exact ops are bit-identical to the oracle; exp / sigmoid may land on the neighbouring code where the device's expf differs by an ulp."""
-    ref, got, _, _ = run_unary(typ, 33, 7, 40, 35, in_dt, out_dt, batch=3)
+    inp = rand_values(np.random.default_rng(15), 3 * 40 * 7, in_dt)
+    ref, got, _, _ = run_unary(typ, 33, 7, 40, 35, in_dt, out_dt, batch=3, inp=inp)
     if typ in (UNARY.SIGMOID, UNARY.EXP):
+        assert_approx(typ, as_float(inp.reshape(3, 7, 40)[:, :, :33], in_dt), as_float(got.reshape(3, 7, 35)[:, :, :33], out_dt), out_dt)
         diff = np.abs(ref.astype(np.int64) - got.astype(np.int64)) if out_dt != DT.F32 else np.abs(ref.view(np.int32).astype(np.int64) - got.view(np.int32).astype(np.int64))
         assert diff.max() <= (1 if out_dt != DT.F32 else 64) and (out_dt == DT.F32 or (diff != 0).mean() < 0.05)
     else:

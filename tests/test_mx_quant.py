@@ -214,6 +214,7 @@ def test_gpu_mx_quant_is_bit_identical(m, n, ldi, ldo, fp4, in_dt):
     p.in_.primary, p.out.primary, p.out.secondary = src.data_ptr(), data.data_ptr(), scales.data_ptr()
     capi.Api.call(h, p)
     api.hip_sync(); api.check()
+    assert api.hip_kernel_name(h, 0).decode() == "mx_quant_kernel"
     gd, gs = mx_quant_gold(x, m, n, ldi, ldo, fp4)
     assert np.array_equal(scales.cpu().numpy(), gs)
     assert np.array_equal(data.cpu().numpy(), gd)
@@ -265,6 +266,7 @@ def test_gpu_nvfp4_quant_is_bit_identical(m, n, ldi, ldo, in_dt):
     p.in_.primary, p.out.primary, p.out.secondary = src.data_ptr(), data.data_ptr(), scales.data_ptr()
     capi.Api.call(h, p)
     api.hip_sync(); api.check()
+    assert api.hip_kernel_name(h, 0).decode() == "nvfp4_quant_kernel"
     gd, gs = nvfp4_gold(x, m, n, ldi, ldo)
     assert np.array_equal(scales.cpu().numpy(), gs)
     assert np.array_equal(data.cpu().numpy(), gd)
