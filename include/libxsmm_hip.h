@@ -232,6 +232,35 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* gr
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
   size_t nsegments, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list);
 
+/* The segments call through an ext handle (libxsmm_dispatch_brgemm_ext with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS): the handle's column bias and activation are
+ * applied per segment inside the one launch, as the reference's fused call applies them [ref: src/generator_gemm_reference_impl.c:294-372]:
+ *   libxsmm_hip_gemm_ext_batch_reduce_segments(kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, d_list, mask_list)
+ *     ==  for (s = 0; s < nsegments; ++s) { q = *param; cnt = seg_ptr[s+1] - seg_ptr[s];
+ *           q.a.primary = (void*)(a_list + seg_ptr[s]);  q.b.primary = (void*)(b_list + seg_ptr[s]);  q.c.primary = c_list[s];
+ *           q.d.primary = d_list ? (void*)d_list[s] : param->d.primary;  q.c.secondary = mask_list ? mask_list[s] : NULL;
+ *           q.op.tertiary = &cnt;  kernel(&q); }
+ * seg_ptr, a_list, b_list and c_list are those of libxsmm_hip_gemm_batch_reduce_segments: device-accessible, read in place, nothing staged, capturable.
+ * d_list holds nsegments pointers to the m-vector bias of C's type (entries may repeat; element alignment only); d_list == NULL on a handle with a column
+ * bias means that param->d.primary -- device-accessible, passed by value in the kernel arguments -- is the bias of every segment.  mask_list holds nsegments
+ * pointers to ReLU bitmask blocks of ((ldc + 15) / 16) * 16 / 8 * n bytes each; it is required exactly when the handle's ReLU carries
+ * LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT and is ignored otherwise.  Overlapping C blocks or overlapping mask blocks are undefined.
+ * Per segment: the accumulator starts at bias[i] (beta = 0), at bias[i] + C(i,j) (beta = 1, one f32 add), or at C(i,j) / +0 without a bias; one chain over
+ * (product, k) in list order; mask bit i % 8 of byte i / 8 + j * (mask_ld / 8) is !(x <= 0) of the sum and is written for i < m, j < n only -- every other
+ * bit and byte of the mask block stays the caller's; then the activation; then one rounding for a bf16 C.  A segment of count 0 is the reference's call with a
+ * count of 0: it stores the activation of the start value (the bias, bias + C, C or +0) and the mask taken from it.
+ * Eligible handles: ADDRESS batch-reduce ext handles under the plain entry's type, layout and flag rules (f32 -> f32, bf16 -> f32 / bf16; A flat or VNNI-2,
+ * B flat, C not VNNI, NN; beta 0 or 1; the hints; element offsets below 2^31) with BINARY_ADD + BCAST_COL_IN_0/1, cp RELU (with or without bitmask), cp
+ * SIGMOID, or no operator at all -- an ext handle without operators is taken for f64 as well and runs the plain kernels.  Errors are set before anything is
+ * launched.  -2: param, seg_ptr, a_list, b_list or c_list is NULL while nsegments > 0; a bias handle with d_list and param->d.primary both NULL; a bitmask
+ * handle with mask_list NULL.  -3: an unknown handle, a non-ext / TPP / equation / sparse handle, a handle that is not ADDRESS batch-reduce, a type, layout,
+ * flag or operator outside the list (the message names which).  -4: no device.  nsegments = 0 does nothing.  Follows the thread's launch mode like the plain
+ * entry.  libxsmm_hip_kernel_name(kernel, 1) names the kernel that ran (gemm_segments_f32_fused_kernel, gemm_segments_bf16_fused_kernel; without operators
+ * the plain entry's kernels).
+ */
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param,
+  size_t nsegments, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list,
+  const void* const* d_list, void* const* mask_list);
+
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns
  * [begin, end) of a `count`-long axis (first `count % world` ranks get one extra unit),

@@ -20,6 +20,7 @@
 #include "internal.hpp"
 #include "gemm_device.hpp"
 #include "bf16_cvt.hpp"
+#include "gemm_tile.hpp"                           // act_fixed: the fused activations
 
 namespace xamd {
 namespace group_tile {
@@ -70,9 +71,31 @@ __device__ __forceinline__ f32x4 mfma_f32(float x, float y, f32x4 acc) { return 
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short v) { return __uint_as_float((unsigned int)v << 16); }
 
-// the accumulator's start value: C (beta = 1) or +0
-template <int T> __device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& g, gptr c, int i, int j0, bool mv, unsigned int lane) {
+// What happens around the chain is a template parameter of the tiles.  NoEpilogue (the default: the grouped kernels and the plain segment kernels) adds
+// nothing -- every use of it sits behind `if constexpr`, so those instances compile to the code they had before the parameter existed.  FusedEpilogue is the
+// ext ABI's epilogue [ref: src/generator_gemm_reference_impl.c:294-372] for one C block: a column bias of C's type added into the start value, the ReLU
+// bitmask taken from the sums, the activation, then the store.  All of its members are wave-uniform (one C block per wave), so they are runtime bits.
+struct NoEpilogue { static constexpr bool fused = false; };
+struct FusedEpilogue {
+  static constexpr bool fused = true;
+  gcptr d;                                         // the block's m-vector bias (colbias != 0)
+  GM unsigned char* mask;                          // the block's ReLU bitmask (act == 2)
+  int colbias, act, mask_ld;                       // act: 0 none, 1 ReLU, 2 ReLU + bitmask, 3 sigmoid (gemm_tile.hpp: act_fixed)
+};
+
+// the accumulator's start value: C (beta = 1) or +0; fused: bias, or bias + C in one f32 add
+template <int T, typename Epi = NoEpilogue>
+__device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& g, gptr c, int i, int j0, bool mv, unsigned int lane, const Epi& e = Epi()) {
   typename Acc<T>::type acc;
+  float bias = 0.0f;
+  bool biased = false;
+  if constexpr (Epi::fused) {
+    biased = e.colbias != 0;
+    if (biased) {                                  // one load per lane, clamped like the operand loads: rows beyond m read row m - 1 and are never stored
+      const int il = min(i, g.m - 1);
+      bias = g.c_bf16 ? bf16_bits_to_f32(((GM const unsigned short*)e.d)[il]) : ((GM const float*)e.d)[il];
+    }
+  }
   static_for<Acc<T>::N>([&](auto r) {
     const int j = j0 + acc_col<T>(r, lane);
     float v = 0.0f;
@@ -80,13 +103,38 @@ template <int T> __device__ __forceinline__ typename Acc<T>::type acc_start(cons
       const long long o = (long long)j * g.ldc + i;
       v = g.c_bf16 ? bf16_bits_to_f32(((GM const unsigned short*)c)[o]) : ((GM const float*)c)[o];
     }
+    if constexpr (Epi::fused) { if (biased) v = g.beta1 ? bias + v : bias; }
     acc[r.value] = v;
   });
   return acc;
 }
 
-template <int T> __device__ __forceinline__ void acc_store(const GemmGroupDesc& g, gptr c, typename Acc<T>::type acc, int i, int j0, bool mv, unsigned int lane) {
+// ReLU bitmask of one tile: bit i % 8 of byte i / 8 + j * (mask_ld / 8) is !(x <= 0) of the sum [ref: mateltwise ref :150-157, :2142].  The lanes hold rows,
+// so a register's ballot is the mask of its two (T = 32) or four (T = 16) columns; the lane with (lane & 7) == 0 owns the byte of its 8 rows.  Tile origins are
+// multiples of 16: a byte never straddles tiles.  Only bits of rows < m, columns < n change: the byte that holds row m - 1 is read, merged and written back.
+template <int T>
+__device__ __forceinline__ void acc_relu_mask(const GemmGroupDesc& g, const FusedEpilogue& e, const typename Acc<T>::type& acc, int i, int j0, bool mv, unsigned int lane) {
+  static_for<Acc<T>::N>([&](auto r) {
+    const int j = j0 + acc_col<T>(r, lane);
+    const bool ok = mv && j < g.n;
+    const unsigned long long pos = __ballot(ok && !(acc[r.value] <= 0.0f));
+    const unsigned long long val = __ballot(ok);
+    if ((lane & 7u) == 0 && ok) {
+      GM unsigned char* byte = e.mask + i / 8 + (long long)j * (e.mask_ld / 8);
+      const unsigned char vm = (unsigned char)((val >> lane) & 0xffu), nb = (unsigned char)((pos >> lane) & 0xffu);
+      *byte = vm == 0xffu ? nb : (unsigned char)((*byte & ~vm) | (nb & vm));
+    }
+  });
+}
+
+template <int T, typename Epi = NoEpilogue>
+__device__ __forceinline__ void acc_store(const GemmGroupDesc& g, gptr c, typename Acc<T>::type acc, int i, int j0, bool mv, unsigned int lane, const Epi& e = Epi()) {
   constexpr int N = Acc<T>::N;
+  if constexpr (Epi::fused) {                      // the mask from the sums, then the activation, then the store below
+    if (e.act == 2) acc_relu_mask<T>(g, e, acc, i, j0, mv, lane);
+    if (e.act == 3) static_for<N>([&](auto r) { acc[r.value] = act_fixed<3>(acc[r.value]); });
+    else if (e.act != 0) static_for<N>([&](auto r) { acc[r.value] = act_fixed<1>(acc[r.value]); });
+  }
   if (g.c_bf16) {
     float x[N]; unsigned int pk[N / 2];
     static_for<N>([&](auto r) { x[r] = acc[r.value]; });
@@ -129,12 +177,13 @@ template <int T, int U> __device__ __forceinline__ void steps_f32(typename Acc<T
 // never stored -- and k beyond K reads k = K - 1 and replaces the value by the -0 / +0 padding.  k advances in blocks of 4 MFMA steps, then one block of up to
 // 4 ragged steps; DEEP puts blocks of 16 steps in front (32 k on a 32-tile: a 32^3 block is ONE round of requests, at 72 more registers) for the kernels
 // whose waves walk long chains alone (segments).  The MFMAs always follow k in natural order.
-template <int T, bool DEEP, typename Chain> __device__ __forceinline__ void tile_f32(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
+template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue>
+__device__ __forceinline__ void tile_f32(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane, const Epi& e = Epi()) {
   constexpr int KS = (T == 32) ? 2 : 4;
   const int lr = (int)(lane & (T - 1)), h = (int)(lane / T);
   const int i = i0 + lr, j = j0 + lr;
   const bool mv = i < g.m;
-  typename Acc<T>::type acc = acc_start<T>(g, c, i, j0, mv, lane);
+  typename Acc<T>::type acc = acc_start<T, Epi>(g, c, i, j0, mv, lane, e);
   const int K = g.k, lda = g.lda;
   const int kbig = K - K % (16 * KS), kfull = K - K % (4 * KS);
   gcptr an = nullptr, bn = nullptr;
@@ -160,7 +209,7 @@ template <int T, bool DEEP, typename Chain> __device__ __forceinline__ void tile
       for (int s = 0; s < 4; ++s) if (kk + s * KS < K) acc = mfma_f32(bv[s], av[s], acc);
     }
   }
-  acc_store<T>(g, c, acc, i, j0, mv, lane);
+  acc_store<T, Epi>(g, c, acc, i, j0, mv, lane, e);
 }
 
 // bf16: lane (i = lane % T, h = lane / T) feeds A(i, k0 + E h + e) and B(k0 + E h + e, j0 + lane % T), e < E, per MFMA: E = 8 for the 32 x 32 x 16
@@ -203,14 +252,15 @@ template <int T, int U, bool VEC> __device__ __forceinline__ void steps_bf16(con
 #pragma unroll
   for (int u = 0; u < U; ++u) acc = mfma_bf16(x[u], y[u], acc);
 }
-template <int T, bool DEEP, typename Chain> __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
+template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue>
+__device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane, const Epi& e = Epi()) {
   constexpr int E = (T == 32) ? 8 : 4, KS = 16;
   typedef typename Frag<E>::type frag;
   const int lr = (int)(lane & (T - 1)), h = (int)(lane / T);
   const int i = i0 + lr, j = j0 + lr;
   const bool mv = i < g.m;
   const int il = min(i, g.m - 1);
-  typename Acc<T>::type acc = acc_start<T>(g, c, i, j0, mv, lane);
+  typename Acc<T>::type acc = acc_start<T, Epi>(g, c, i, j0, mv, lane, e);
   const int K = g.k;
   const int kbig = K - K % (4 * KS), kfull = K - K % KS;
   gcptr an = nullptr, bn = nullptr;
@@ -240,7 +290,7 @@ template <int T, bool DEEP, typename Chain> __device__ __forceinline__ void tile
       acc = mfma_bf16(x, y, acc);
     }
   }
-  acc_store<T>(g, c, acc, i, j0, mv, lane);
+  acc_store<T, Epi>(g, c, acc, i, j0, mv, lane, e);
 }
 
 // f64, one 16 x 16 tile: lane (g = lane % 16, s = lane / 16) feeds A(i0 + g, k0 + s) and B(k0 + s, j0 + g) per MFMA and holds C(i0 + g, j0 + s + 4 r) in

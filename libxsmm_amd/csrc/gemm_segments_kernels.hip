@@ -10,6 +10,11 @@
 // is never split.  A segment of count 0 stores beta * C (beta = 0: +0; beta = 1: C's own bits).  No LDS, no barrier, no scratch; C leaves through vector stores.
 // Block pointers are only known to be element-aligned: 16- / 8-byte loads of B columns and 4-byte loads of VNNI A pairs are chosen per product by a
 // wave-uniform test of the pointer, the element-wise loads remain for every other product.
+//
+// libxsmm_hip_gemm_ext_batch_reduce_segments runs the same items through gemm_segments_f32_fused_kernel / _bf16_fused_kernel: the tiles take a FusedEpilogue
+// (gemm_group_tile.hpp) whose bias and mask pointers are d_list[s] and mask_list[s], read like c_list[s]; the operators are wave-uniform runtime bits of a small
+// by-value block (GemmSegEpilogue) next to the GemmGroupDesc.  A segment of count 0 stores the activation of its start value (the bias, bias + C) and its mask.
+// The plain kernels above are instantiated with the default epilogue and are instruction for instruction what they were without it.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "internal.hpp"
@@ -21,10 +26,11 @@ namespace xamd {
 
 using namespace group_tile;
 
-// CLS: 0 f32, 1 bf16, 2 f64
-template <int CLS>
+// CLS: 0 f32, 1 bf16, 2 f64.  FUSED: the ext ABI's epilogue per segment (libxsmm_hip_gemm_ext_batch_reduce_segments); d_list[s] and mask_list[s] are wave-uniform
+// like c_list[s] and are read the same way.
+template <int CLS, bool FUSED = false>
 __device__ __forceinline__ void segments_body(const GemmGroupDesc& g, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list,
-  void* const* c_list, unsigned long long total) {
+  void* const* c_list, unsigned long long total, const GemmSegEpilogue* ep = nullptr) {
   const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const unsigned int lane = threadIdx.x & 63u;
   const unsigned long long step = (unsigned long long)gridDim.x * 4u;
@@ -36,7 +42,16 @@ __device__ __forceinline__ void segments_body(const GemmGroupDesc& g, const unsi
     const unsigned long long r0 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s]), r1 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s + 1]);
     gptr c = (gptr)list_entry((const void*)c_list, s);
     const ListChain ch{(const void*)(a_list + r0), (const void*)(b_list + r0), r1 - r0, g.a_vec4, g.b_vec16, g.b_vec8};
-    if constexpr (CLS == 2) tile_f64(g, ch, c, (int)tm * 16, (int)tn * 16, lane);
+    if constexpr (FUSED) {
+      FusedEpilogue e{(gcptr)ep->d, nullptr, ep->colbias, ep->act, ep->mask_ld};
+      if (ep->colbias && ep->d_list) e.d = list_entry((const void*)ep->d_list, s);
+      if (ep->act == 2) e.mask = (GM unsigned char*)list_entry((const void*)ep->mask_list, s);
+      if (g.tile == 32) {
+        if constexpr (CLS == 1) tile_bf16<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane, e); else tile_f32<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane, e);
+      } else {
+        if constexpr (CLS == 1) tile_bf16<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane, e); else tile_f32<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane, e);
+      }
+    } else if constexpr (CLS == 2) tile_f64(g, ch, c, (int)tm * 16, (int)tn * 16, lane);
     else if (g.tile == 32) {
       if constexpr (CLS == 1) tile_bf16<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane); else tile_f32<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane);
     } else {
@@ -52,6 +67,15 @@ __global__ __launch_bounds__(256) void gemm_segments_bf16_kernel(GemmGroupDesc g
 __global__ __launch_bounds__(256) void gemm_segments_f64_kernel(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list,
   const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { segments_body<2>(g, seg_ptr, a_list, b_list, c_list, total); }
 
+__global__ __launch_bounds__(256) void gemm_segments_f32_fused_kernel(GemmGroupDesc g, GemmSegEpilogue e, const unsigned long long* __restrict__ seg_ptr,
+  const void* const* __restrict__ a_list, const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) {
+  segments_body<0, true>(g, seg_ptr, a_list, b_list, c_list, total, &e);
+}
+__global__ __launch_bounds__(256) void gemm_segments_bf16_fused_kernel(GemmGroupDesc g, GemmSegEpilogue e, const unsigned long long* __restrict__ seg_ptr,
+  const void* const* __restrict__ a_list, const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) {
+  segments_body<1, true>(g, seg_ptr, a_list, b_list, c_list, total, &e);
+}
+
 const char* gemm_segments_kernel_name(int cls) { return cls == 2 ? "gemm_segments_f64_kernel" : (cls == 1 ? "gemm_segments_bf16_kernel" : "gemm_segments_f32_kernel"); }
 
 int launch_gemm_segments(const GemmGroupDesc& g, int cls, unsigned long long items, const unsigned long long* seg_ptr, const void* const* a_list,
@@ -63,6 +87,18 @@ int launch_gemm_segments(const GemmGroupDesc& g, int cls, unsigned long long ite
   if (cls == 2) hipLaunchKernelGGL(gemm_segments_f64_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
   else if (cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
   else hipLaunchKernelGGL(gemm_segments_f32_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
+  return (int)hipGetLastError();
+}
+
+const char* gemm_segments_fused_kernel_name(int cls) { return cls == 1 ? "gemm_segments_bf16_fused_kernel" : "gemm_segments_f32_fused_kernel"; }
+
+int launch_gemm_segments_fused(const GemmGroupDesc& g, const GemmSegEpilogue& e, int cls, unsigned long long items, const unsigned long long* seg_ptr,
+  const void* const* a_list, const void* const* b_list, void* const* c_list, void* stream) {
+  if (items == 0) return 0;
+  const unsigned int grid = (unsigned int)std::min<unsigned long long>((items + 3) / 4, 32768ull);     // the plain launch's rule
+  hipStream_t st = (hipStream_t)stream;
+  if (cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, g, e, seg_ptr, a_list, b_list, c_list, items);
+  else hipLaunchKernelGGL(gemm_segments_f32_fused_kernel, dim3(grid), dim3(256), 0, st, g, e, seg_ptr, a_list, b_list, c_list, items);
   return (int)hipGetLastError();
 }
 

@@ -121,6 +121,13 @@ struct GemmGroupDesc {
   int b_vec16, b_vec8;                              // B columns 16- / 8-byte aligned (every element, every block)
 };
 static_assert(sizeof(GemmGroupDesc) == 144, "the grouped kernels' table entry");
+// libxsmm_hip_gemm_ext_batch_reduce_segments: the fused epilogue of a segments call, by value in the kernel arguments next to the GemmGroupDesc
+struct GemmSegEpilogue {
+  const void* const* d_list;                        // one m-vector bias of C's type per segment, or NULL: `d` is shared by every segment
+  const char* d;
+  void* const* mask_list;                           // one ReLU bitmask block per segment (act == 2)
+  int colbias, act, mask_ld;                        // act: 0 none, 1 ReLU, 2 ReLU + bitmask, 3 sigmoid; mask_ld = ldc rounded up to 16
+};
 
 // sparse operator S (rows x inner) applied to a packed panel:
 //   Y[r][q] (+)= sum_z val[z] * X[idx[z]][q],   q = 0..ncols-1 contiguous, for `nouter` slabs
@@ -299,6 +306,10 @@ const char* gemm_grouped_kernel_name(int bf16);
 int launch_gemm_segments(const GemmGroupDesc& g, int cls, unsigned long long items, const unsigned long long* seg_ptr, const void* const* a_list,
   const void* const* b_list, void* const* c_list, void* stream);
 const char* gemm_segments_kernel_name(int cls);
+// the same launch with the ext ABI's epilogue (column bias, ReLU (+ bitmask), sigmoid) fused into the store; cls 0 or 1
+int launch_gemm_segments_fused(const GemmGroupDesc& g, const GemmSegEpilogue& e, int cls, unsigned long long items, const unsigned long long* seg_ptr,
+  const void* const* a_list, const void* const* b_list, void* const* c_list, void* stream);
+const char* gemm_segments_fused_kernel_name(int cls);
 int launch_spmm(const SpmmArgs& args, void* stream, const char** kernel_name);
 int launch_bcsc(const BcscArgs& args, void* stream, const char** kernel_name);
 // Automatic streaming decision (libxsmm_hip_set_streaming_hint(0)): a launch whose own operands exceed the Infinity Cache streams -- and so does a launch whose operands

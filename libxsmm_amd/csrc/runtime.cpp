@@ -2331,39 +2331,44 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* gr
 // ---- segments (libxsmm_hip_gemm_batch_reduce_segments): ADDRESS batch-reduce with a count per C block, one launch -------------------------------------
 // The count is the one argument of a BRGEMM call that the reference re-reads on every call [ref: gemm ref :490-492]; here it is seg_ptr[s + 1] - seg_ptr[s].
 // Nothing is staged or uploaded: the four arrays are read on the device as they are, the shape travels in the kernel arguments, so the call can be captured.
-LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
-  const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list) {
-  static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments";
-  if (nsegments == 0) return;
+// What both segments entries ask of their arguments and their handle, in one place: every refusal is set here, before anything is launched.  `ext` is the
+// entry (libxsmm_hip_gemm_ext_batch_reduce_segments takes ext handles and only those); on success `g` holds the shape as the kernels read it, `cls` the
+// kernel class (0 f32, 1 bf16, 2 f64) and `tiles` the C tiles of one segment.
+static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, const unsigned long long* seg_ptr,
+  const void* const* a_list, const void* const* b_list, void* const* c_list, GemmGroupDesc& g, int& cls, unsigned long long& tiles) {
   if (!param || !seg_ptr || !a_list || !b_list || !c_list) {
-    set_error(-2, "%s: %s is NULL but nsegments = %zu", fn, !param ? "param" : (!seg_ptr ? "seg_ptr" : (!a_list ? "a_list" : (!b_list ? "b_list" : "c_list"))), nsegments); return;
+    set_error(-2, "%s: %s is NULL but nsegments = %zu", fn, !param ? "param" : (!seg_ptr ? "seg_ptr" : (!a_list ? "a_list" : (!b_list ? "b_list" : "c_list"))), nsegments); return nullptr;
   }
-  KernelCtx* k = ctx_from_handle((const void*)kernel);
-  if (!k) { set_error(-3, "%s: unknown kernel handle", fn); return; }
-  if (k->kind != K_GEMM) { set_error(-3, "%s: handle is not a BRGEMM kernel (TPP, equation and sparse handles are not taken)", fn); return; }
+  KernelCtx* k = ctx_from_handle(kernel);
+  if (!k) { set_error(-3, "%s: unknown kernel handle", fn); return nullptr; }
+  if (k->kind != K_GEMM) { set_error(-3, "%s: handle is not a BRGEMM kernel (TPP, equation and sparse handles are not taken)", fn); return nullptr; }
   const libxsmm_gemm_descriptor& d = k->g;
-  if (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI) { set_error(-3, "%s: ext handles are not taken", fn); return; }
-  if (!(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS)) { set_error(-3, "%s: handle is not an ADDRESS batch-reduce kernel (libxsmm_dispatch_brgemm with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS)", fn); return; }
+  const bool is_ext = (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI) != 0;
+  if (!ext && is_ext) { set_error(-3, "%s: ext handles are not taken", fn); return nullptr; }
+  if (ext && !is_ext) { set_error(-3, "%s: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_reduce_segments)", fn); return nullptr; }
+  if (!(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS)) {
+    set_error(-3, "%s: handle is not an ADDRESS batch-reduce kernel (%s with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS)", fn, ext ? "libxsmm_dispatch_brgemm_ext" : "libxsmm_dispatch_brgemm"); return nullptr;
+  }
   const bool f32 = d.a_type == LIBXSMM_DATATYPE_F32 && d.b_type == LIBXSMM_DATATYPE_F32 && d.c_type == LIBXSMM_DATATYPE_F32;
   const bool f64 = d.a_type == LIBXSMM_DATATYPE_F64 && d.b_type == LIBXSMM_DATATYPE_F64 && d.c_type == LIBXSMM_DATATYPE_F64;
   const bool bf16 = d.a_type == LIBXSMM_DATATYPE_BF16 && d.b_type == LIBXSMM_DATATYPE_BF16 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF16);
   if (!f32 && !f64 && !bf16) {
-    set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return;
+    set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return nullptr;
   }
   const unsigned int f = effective_gemm_flags(d);
-  if (f & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return; }
-  if (f & (LIBXSMM_GEMM_FLAG_VNNI_B | LIBXSMM_GEMM_FLAG_VNNI_C)) { set_error(-3, "%s: VNNI layouts of B and C are not taken (A flat or VNNI-2, B and C flat)", fn); return; }
+  if (f & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return nullptr; }
+  if (f & (LIBXSMM_GEMM_FLAG_VNNI_B | LIBXSMM_GEMM_FLAG_VNNI_C)) { set_error(-3, "%s: VNNI layouts of B and C are not taken (A flat or VNNI-2, B and C flat)", fn); return nullptr; }
   const unsigned int allowed = LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_ALIGN_A | LIBXSMM_GEMM_FLAG_ALIGN_C_NTS_HINT | LIBXSMM_GEMM_FLAG_NO_RESET_TILECONFIG |
-    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS;
-  if (f & ~allowed) { set_error(-3, "%s: flags 0x%x are not taken (beta, VNNI_A and the hints only)", fn, f & ~allowed); return; }
+    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS |
+    (ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
+  if (f & ~allowed) { set_error(-3, "%s: flags 0x%x are not taken (beta, VNNI_A and the hints only)", fn, f & ~allowed); return nullptr; }
   // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers): the grouped kernels' bound
   const unsigned long long lim = 1ull << 31;
   if ((unsigned long long)d.lda * (d.k + 1) >= lim || (unsigned long long)d.ldb * d.n >= lim || (unsigned long long)d.ldc * d.n >= lim) {
-    set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return;
+    set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return nullptr;
   }
-  const int cls = f64 ? 2 : (bf16 ? 1 : 0);
+  cls = f64 ? 2 : (bf16 ? 1 : 0);
   const int tile = (f64 || (d.m <= 16 && d.n <= 16)) ? 16 : 32;
-  GemmGroupDesc g;
   std::memset(&g, 0, sizeof(g));
   g.m = (int)d.m; g.n = (int)d.n; g.k = (int)d.k; g.lda = (int)d.lda; g.ldb = (int)d.ldb; g.ldc = (int)d.ldc;
   g.tile = tile; g.tiles_m = (int)((d.m + tile - 1) / tile); g.tiles_n = (int)((d.n + tile - 1) / tile);
@@ -2373,14 +2378,65 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction ker
   // what the leading dimension allows of the wider loads; the block pointers are tested per product on the device
   const unsigned long long colb = (unsigned long long)d.ldb * (bf16 ? 2 : (f64 ? 8 : 4));
   g.a_vec4 = bf16 ? 1 : 0; g.b_vec16 = (colb & 15) == 0 ? 1 : 0; g.b_vec8 = (colb & 7) == 0 ? 1 : 0;
-  const unsigned long long tiles = (unsigned long long)g.tiles_m * (unsigned long long)g.tiles_n;
-  if (tiles != 0 && (unsigned long long)nsegments > ~0ull / tiles - 4) { set_error(-3, "%s: nsegments x C tiles overflows 64 bits", fn); return; }
+  tiles = (unsigned long long)g.tiles_m * (unsigned long long)g.tiles_n;
+  if (tiles != 0 && (unsigned long long)nsegments > ~0ull / tiles - 4) { set_error(-3, "%s: nsegments x C tiles overflows 64 bits", fn); return nullptr; }
+  return k;
+}
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
+  const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list) {
+  static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments";
+  if (nsegments == 0) return;
+  GemmGroupDesc g; int cls = 0; unsigned long long tiles = 0;
+  KernelCtx* k = segments_validate(fn, false, (const void*)kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, g, cls, tiles);
+  if (!k) return;
   coalesce_flush();
   if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
   scratch_reset();
   if (tiles == 0) return;                               // m or n is 0: no C
   const char* kname = gemm_segments_kernel_name(cls);
   const int err = launch_gemm_segments(g, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream);
+  k->kname_batched = kname;
+  finish_launch(err, kname);
+}
+// The same call through an ext handle (libxsmm_dispatch_brgemm_ext): the column bias, the ReLU (+ bitmask) or the sigmoid of the handle are applied per
+// segment inside the launch, as the reference's fused call does [ref: gemm ref :294-372].  The operators are decoded as run_gemm decodes them; the bias and mask
+// blocks come from two more device-accessible lists (or one shared bias by value), so this call, too, stages nothing and can be captured.
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param, size_t nsegments,
+  const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list, const void* const* d_list, void* const* mask_list) {
+  static const char* const fn = "libxsmm_hip_gemm_ext_batch_reduce_segments";
+  if (nsegments == 0) return;
+  GemmGroupDesc g; int cls = 0; unsigned long long tiles = 0;
+  KernelCtx* k = segments_validate(fn, true, (const void*)kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, g, cls, tiles);
+  if (!k) return;
+  const libxsmm_gemm_descriptor& d = k->g;
+  GemmSegEpilogue e;
+  std::memset(&e, 0, sizeof(e));
+  const bool colbias = d.bin_type == LIBXSMM_MELTW_TYPE_BINARY_ADD && (d.bin_flags & (LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_0 | LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_1));
+  if ((d.bin_type != LIBXSMM_MELTW_TYPE_BINARY_NONE && !colbias) || d.ap_type != 0 || d.bp_type != 0 ||
+      (d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_NONE && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_RELU && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_SIGMOID)) {
+    set_error(-3, "%s: fused operator not taken (column-broadcast BINARY_ADD, cp RELU with or without bitmask, cp SIGMOID only)", fn); return;
+  }
+  e.colbias = colbias ? 1 : 0;
+  if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_RELU) e.act = (d.cp_flags & LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT) ? 2 : 1;
+  else if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_SIGMOID) e.act = 3;
+  const bool fused = e.colbias != 0 || e.act != 0;
+  if (cls == 2 && fused) { set_error(-3, "%s: f64 ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return; }
+  if (e.colbias) {
+    e.d_list = d_list; e.d = (const char*)param->d.primary;
+    if (!d_list && !e.d) { set_error(-2, "%s: fused column bias requested but d_list and param->d.primary are both NULL", fn); return; }
+  }
+  if (e.act == 2) {
+    e.mask_list = mask_list; e.mask_ld = ((int)d.ldc + 15) / 16 * 16;
+    if (!mask_list) { set_error(-2, "%s: ReLU bitmask requested but mask_list is NULL", fn); return; }
+  }
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  if (tiles == 0) return;                               // m or n is 0: no C
+  // an ext handle without operators is the plain product: it runs the plain kernels (f64 among them)
+  const char* kname = fused ? gemm_segments_fused_kernel_name(cls) : gemm_segments_kernel_name(cls);
+  const int err = fused ? launch_gemm_segments_fused(g, e, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream)
+                        : launch_gemm_segments(g, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream);
   k->kname_batched = kname;
   finish_launch(err, kname);
 }
