@@ -261,6 +261,35 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction
   size_t nsegments, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list,
   const void* const* d_list, void* const* mask_list);
 
+/* Segments through an OFFSET batch-reduce handle (libxsmm_dispatch_brgemm with LIBXSMM_GEMM_BATCH_REDUCE_OFFSET), with transposed operands accepted: the
+ * forward AND the backward passes of a block-sparse layer as one launch each -- Y = W X (NN), dX = W^T dY (LIBXSMM_GEMM_FLAG_TRANS_A, the lists in block-column
+ * order over the same W buffer), dW_b = sum_n dY_n X_n^T (LIBXSMM_GEMM_FLAG_TRANS_B) -- from lists that do not depend on where the operands lie
+ * [ref: src/generator_gemm_reference_impl.c:509-513, :186-188]:
+ *   libxsmm_hip_gemm_batch_reduce_segments_offsets(kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs)
+ *     ==  for (s = 0; s < nsegments; ++s) { q = *param; cnt = seg_ptr[s+1] - seg_ptr[s];
+ *           q.a.secondary = (void*)(a_offs + seg_ptr[s]);  q.b.secondary = (void*)(b_offs + seg_ptr[s]);
+ *           q.c.primary   = (char*)param->c.primary + c_offs[s];  q.op.tertiary = &cnt;  kernel(&q); }
+ * param->a.primary, b.primary and c.primary are the three bases: device-accessible, and passed BY VALUE in the kernel arguments -- a call captured into a
+ * graph replays on the same three bases (overwrite the operands in place, or capture one call per buffer).  seg_ptr holds nsegments + 1 entries, CSR-style
+ * and non-decreasing; a_offs and b_offs hold seg_ptr[nsegments] signed byte offsets each, c_offs nsegments.  All four arrays must be device-accessible and are
+ * read in place: nothing is staged or uploaded, so the call may be captured, and a caller whose pattern is fixed computes the lists once and only moves the
+ * bases -- another layer's activations, dY instead of X, the other half of a double buffer.  param's other slots are ignored.  Segments whose C blocks overlap
+ * are undefined; A and B blocks may be shared freely.  Order, start value and count 0 are those of libxsmm_hip_gemm_batch_reduce_segments: one accumulator
+ * chain over (product, k) in list order from C (beta = 1) or +0; a segment of count 0 stores beta * C; for f32 the result is the k-ordered fmaf chain bit for
+ * bit, in every form.  Work is handed out in list order; a segment is never split.
+ * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16.  A flat, A with TRANS_A (flat, A(i,k) at i * lda + k, lda >= k) or, for
+ * bf16, VNNI-2 without TRANS_A; B flat or B with TRANS_B (flat, B(k,j) at k * ldb + j, ldb >= n); both transposes together are allowed; VNNI_B and VNNI_C are
+ * refused; beta 0 or 1; no flag beyond those and the hints; element offsets inside one operand (lda * m and ldb * k for transposed ones) stay below 2^31.
+ * Offsets need element alignment only.  Follows the thread's launch mode: blocking, stream-ordered, coalescing (the queue is flushed first), inside a pipeline
+ * section.  Errors are set before anything is launched, one per refusal.  -2: param, seg_ptr, a_offs, b_offs, c_offs or one of the three bases is NULL while
+ * nsegments > 0; -3: an unknown handle, a TPP / equation / sparse / ext handle, a GEMM handle that is not OFFSET batch-reduce, or a type, layout or flag
+ * outside the list above (the message names which); -4: no device.  nsegments = 0 does nothing.  libxsmm_hip_kernel_name(kernel, 1) names the kernel that
+ * ran (gemm_segments_offs_f32_kernel<ta,tb>, _f64_kernel<ta,tb>, _bf16_kernel<ta,tb>: one instance per pair of transposes).  The two ADDRESS entries above keep refusing transposed operands; the fused (ext) form
+ * has no OFFSET entry.
+ */
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
+  size_t nsegments, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs);
+
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns
  * [begin, end) of a `count`-long axis (first `count % world` ranks get one extra unit),

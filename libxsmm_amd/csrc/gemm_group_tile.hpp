@@ -3,6 +3,7 @@
 // Where the blocks of the chain lie is the only thing the two users differ in, so it is a template parameter:
 //   StrideChain   block r = base + r * stride                                   (STRIDE batch-reduce; count 1 for plain GEMM handles)
 //   ListChain     block r = a_list[r], b_list[r], read with scalar loads         (ADDRESS batch-reduce with a count of its own per segment)
+//   OffsetChain   block r = a + a_offs[r], b + b_offs[r], read the same way      (OFFSET batch-reduce segments: two bases by value, signed byte offsets)
 // A chain hands out block r + 1 while block r is being multiplied (fetch), so a list chain's dependent address -> data round trip overlaps the MFMAs, and it
 // answers the alignment questions of the wider loads per block (a stride chain answers with what the host worked out for the whole group).
 //
@@ -15,6 +16,15 @@
 // beta = 1 starts the chain at C.  Ragged k is padded with A = -0.0 and B = +0.0: adding the product -0 is an exact identity for every accumulator
 // (+0 + -0 = +0 under round-to-nearest), so the f32 chain stays bitwise.  Rows and columns beyond m / n load the last valid row / column and are never
 // stored, so no access leaves the caller's operands.
+// Transposed operands (template arguments TA / TB, NN by default: the instances without them are instruction for instruction what they were) swap the two load
+// forms a tile has.  An operand is either contiguous over the LANES and strided in k (flat A: A(i, k) at k * lda + i; TRANS_B: B(k, j) at k * ldb + j) or
+// contiguous in K per lane (flat B: B(k, j) at j * ldb + k; TRANS_A: A(i, k) at i * lda + k).  A transposed A therefore takes B's loads -- 16-byte pieces of
+// the lane's k run for f32 (each lane half picks its odd or even k), one 16- or 8-byte load per MFMA step for bf16, chosen per product from the pointer and
+// the leading dimension -- and a transposed B takes flat A's element loads.  f64 loads elements in both forms: lane s of a 16 x 16 x 4 step owns the k with
+// k % 4 == s, so no two k of a lane are neighbours and a pair load would fetch one element it cannot use; the four lanes of a row still cover one 32-byte sector.
+// The clamping is that of the NN forms: a wide load starts at i * lda + kk inside a whole k block (kk + its width <= K <= lda), rows and columns beyond m / n
+// read row m - 1 / column n - 1, ragged k reads k = K - 1 -- the last element touched is (m - 1) * lda + K - 1 of a TRANS_A block, (K - 1) * ldb + n - 1 of a
+// TRANS_B block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "internal.hpp"
@@ -51,6 +61,28 @@ struct ListChain {
   __device__ __forceinline__ bool b_vec16(gcptr p) const { return vb16 != 0 && ((unsigned int)(size_t)p & 15u) == 0; }
   __device__ __forceinline__ bool b_vec8(gcptr p) const { return vb8 != 0 && ((unsigned int)(size_t)p & 7u) == 0; }
 };
+
+// The OFFSET form of a list chain [ref: src/generator_gemm_reference_impl.c:186-188]: `oa` / `ob` point at the chain's first signed byte offset, `a` / `b` are the
+// bases every offset is added to.  Same prefetch, same re-read of the last entry at fetch(count).  The alignment questions are asked of the resulting pointer;
+// `va16` / `va8` say whether the leading dimension of a TRANSPOSED A allows 16- / 8-byte loads of a row's k run.
+struct OffsetChain {
+  gcptr a, b; const void* oa; const void* ob; unsigned long long count;
+  int va4, vb16, vb8, va16, va8;
+  __device__ __forceinline__ void fetch(unsigned long long r, gcptr& pa, gcptr& pb) const {
+    const unsigned long long rc = r < count ? r : count - 1;
+    pa = a + (long long)uniform_u64(((GM const unsigned long long*)oa)[rc]); pb = b + (long long)uniform_u64(((GM const unsigned long long*)ob)[rc]);
+  }
+  __device__ __forceinline__ bool a_vec4(gcptr p) const { return va4 != 0 && ((unsigned int)(size_t)p & 3u) == 0; }
+  __device__ __forceinline__ bool a_vec16(gcptr p) const { return va16 != 0 && ((unsigned int)(size_t)p & 15u) == 0; }
+  __device__ __forceinline__ bool a_vec8(gcptr p) const { return va8 != 0 && ((unsigned int)(size_t)p & 7u) == 0; }
+  __device__ __forceinline__ bool b_vec16(gcptr p) const { return vb16 != 0 && ((unsigned int)(size_t)p & 15u) == 0; }
+  __device__ __forceinline__ bool b_vec8(gcptr p) const { return vb8 != 0 && ((unsigned int)(size_t)p & 7u) == 0; }
+};
+
+// element index of k in a lane's operand pointer: KC (contiguous in k: flat B, TRANS_A) k itself, else (contiguous over the lanes: flat A, TRANS_B) k * ld;
+// and of the lane's row / column x where that pointer starts
+template <bool KC> __device__ __forceinline__ int k_index(int k, int ld) { if constexpr (KC) return k; else return k * ld; }
+template <bool KC> __device__ __forceinline__ long long lane_index(int x, int ld) { if constexpr (KC) return (long long)x * ld; else return x; }
 
 // accumulator register r of lane `lane` holds C column (j0 +) acc_col<T>(r, lane), C row (i0 +) lane % T
 template <int T> __device__ __forceinline__ int acc_col(int r, unsigned int lane) {
@@ -153,12 +185,30 @@ __device__ __forceinline__ void acc_store(const GemmGroupDesc& g, gptr c, typena
 
 // U consecutive MFMA steps of an f32 tile from k = kk on: all operand requests of the steps go out before the first MFMA, so a block of U steps pays the
 // memory latency once.  b_vec: B(kk .. kk + 2 U - 1) of the lane's column in 16-byte pieces (32-tiles); lane half h takes the odd or even k of a piece.
-template <int T, int U> __device__ __forceinline__ void steps_f32(typename Acc<T>::type& acc, GM const float* ap, GM const float* bp, int kk, int lda, int h, bool b_vec) {
+// TA: A's k run is the contiguous one and takes the same pieces under a_vec; TB: B is read like flat A, element by element at k * ldb.
+template <int T, int U, bool TA = false, bool TB = false>
+__device__ __forceinline__ void steps_f32(typename Acc<T>::type& acc, GM const float* ap, GM const float* bp, int kk, int lda, int h, bool b_vec, int ldb = 0, bool a_vec = false) {
   constexpr int KS = (T == 32) ? 2 : 4;
   float av[U], bv[U];
+  if constexpr (TA) {
+    if (T == 32 && a_vec) {
 #pragma unroll
-  for (int s = 0; s < U; ++s) av[s] = ap[(kk + s * KS + h) * lda];
-  if (T == 32 && b_vec) {
+      for (int q = 0; q < U / 2; ++q) {
+        const f32x4 v = *(GM const f32x4*)(ap + kk + 4 * q);
+        av[2 * q] = h ? v[1] : v[0]; av[2 * q + 1] = h ? v[3] : v[2];
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < U; ++s) av[s] = ap[kk + s * KS + h];
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < U; ++s) av[s] = ap[(kk + s * KS + h) * lda];
+  }
+  if constexpr (TB) {
+#pragma unroll
+    for (int s = 0; s < U; ++s) bv[s] = bp[(kk + s * KS + h) * ldb];
+  } else if (T == 32 && b_vec) {
 #pragma unroll
     for (int q = 0; q < U / 2; ++q) {
       const f32x4 v = *(GM const f32x4*)(bp + kk + 4 * q);
@@ -177,32 +227,34 @@ template <int T, int U> __device__ __forceinline__ void steps_f32(typename Acc<T
 // never stored -- and k beyond K reads k = K - 1 and replaces the value by the -0 / +0 padding.  k advances in blocks of 4 MFMA steps, then one block of up to
 // 4 ragged steps; DEEP puts blocks of 16 steps in front (32 k on a 32-tile: a 32^3 block is ONE round of requests, at 72 more registers) for the kernels
 // whose waves walk long chains alone (segments).  The MFMAs always follow k in natural order.
-template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue>
+template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue, bool TA = false, bool TB = false>
 __device__ __forceinline__ void tile_f32(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane, const Epi& e = Epi()) {
   constexpr int KS = (T == 32) ? 2 : 4;
   const int lr = (int)(lane & (T - 1)), h = (int)(lane / T);
   const int i = i0 + lr, j = j0 + lr;
   const bool mv = i < g.m;
   typename Acc<T>::type acc = acc_start<T, Epi>(g, c, i, j0, mv, lane, e);
-  const int K = g.k, lda = g.lda;
+  const int K = g.k, lda = g.lda, ldb = g.ldb;
   const int kbig = K - K % (16 * KS), kfull = K - K % (4 * KS);
   gcptr an = nullptr, bn = nullptr;
   if (ch.count) ch.fetch(0, an, bn);
   for (unsigned long long r = 0; r < ch.count; ++r) {
     const gcptr a = an, b = bn;
     ch.fetch(r + 1, an, bn);                   // the next block's addresses are on their way while this block is multiplied
-    GM const float* ap = (GM const float*)a + min(i, g.m - 1);
-    GM const float* bp = (GM const float*)b + (long long)min(j, g.n - 1) * g.ldb;
-    const bool b_vec = T == 32 && ch.b_vec16(b);
+    GM const float* ap = (GM const float*)a + lane_index<TA>(min(i, g.m - 1), lda);
+    GM const float* bp = (GM const float*)b + lane_index<!TB>(min(j, g.n - 1), g.ldb);
+    bool b_vec = false, a_vec = false;
+    if constexpr (!TB) b_vec = T == 32 && ch.b_vec16(b);
+    if constexpr (TA) a_vec = T == 32 && ch.a_vec16(a);
     int kk = 0;
-    if constexpr (DEEP) for (; kk < kbig; kk += 16 * KS) steps_f32<T, 16>(acc, ap, bp, kk, lda, h, b_vec);
-    for (; kk < kfull; kk += 4 * KS) steps_f32<T, 4>(acc, ap, bp, kk, lda, h, b_vec);
+    if constexpr (DEEP) for (; kk < kbig; kk += 16 * KS) steps_f32<T, 16, TA, TB>(acc, ap, bp, kk, lda, h, b_vec, ldb, a_vec);
+    for (; kk < kfull; kk += 4 * KS) steps_f32<T, 4, TA, TB>(acc, ap, bp, kk, lda, h, b_vec, ldb, a_vec);
     if (kk < K) {                              // ragged k, up to four steps: A = -0, B = +0 beyond K
       float av[4], bv[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const int kx = kk + s * KS + h, kc = min(kx, K - 1);
-        const float va = ap[kc * lda], vb = bp[kc];
+        const float va = ap[k_index<TA>(kc, lda)], vb = bp[k_index<!TB>(kc, ldb)];
         av[s] = kx < K ? va : -0.0f; bv[s] = kx < K ? vb : 0.0f;
       }
 #pragma unroll
@@ -224,7 +276,9 @@ __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 x, bf16x8 y, f32x16 acc) { re
 __device__ __forceinline__ f32x4 mfma_bf16(bf16x4 x, bf16x4 y, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(x, y, acc, 0, 0, 0); }
 // U consecutive MFMA steps (16 k each) of a bf16 tile from k = kk on, every operand request ahead of the first MFMA; VEC: both operands are known to take
 // the wide loads (no element-wise code in the instance)
-template <int T, int U, bool VEC> __device__ __forceinline__ void steps_bf16(const GemmGroupDesc& g, typename Acc<T>::type& acc, GM const unsigned short* ap, GM const unsigned short* bp,
+// TA: `ap` is the lane's row of a transposed A and a step is ONE 16- / 8-byte load of its k run under a_vec (B's form); TB: `bp` is the lane's column of a
+// transposed B, read element by element at k * ldb (flat A's form)
+template <int T, int U, bool VEC, bool TA = false, bool TB = false> __device__ __forceinline__ void steps_bf16(const GemmGroupDesc& g, typename Acc<T>::type& acc, GM const unsigned short* ap, GM const unsigned short* bp,
   int kk, int il, int h, bool a_vec, bool b_vec) {
   constexpr int E = (T == 32) ? 8 : 4, KS = 16;
   typedef typename Frag<E>::type frag;
@@ -233,12 +287,21 @@ template <int T, int U, bool VEC> __device__ __forceinline__ void steps_bf16(con
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int k0 = kk + u * KS + E * h;
-    if (VEC || b_vec) x[u] = __builtin_bit_cast(frag, *(GM const words*)(bp + k0));
+    if constexpr (TB) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) x[u][e] = (short)bp[(k0 + e) * g.ldb];
+    } else if (VEC || b_vec) x[u] = __builtin_bit_cast(frag, *(GM const words*)(bp + k0));
     else {
 #pragma unroll
       for (int e = 0; e < E; ++e) x[u][e] = (short)bp[k0 + e];
     }
-    if (VEC || a_vec) {
+    if constexpr (TA) {
+      if (VEC || a_vec) y[u] = __builtin_bit_cast(frag, *(GM const words*)(ap + k0));
+      else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) y[u][e] = (short)ap[k0 + e];
+      }
+    } else if (VEC || a_vec) {
       GM const unsigned int* ap4 = (GM const unsigned int*)ap;
       words w;
 #pragma unroll
@@ -252,7 +315,7 @@ template <int T, int U, bool VEC> __device__ __forceinline__ void steps_bf16(con
 #pragma unroll
   for (int u = 0; u < U; ++u) acc = mfma_bf16(x[u], y[u], acc);
 }
-template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue>
+template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue, bool TA = false, bool TB = false>
 __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane, const Epi& e = Epi()) {
   constexpr int E = (T == 32) ? 8 : 4, KS = 16;
   typedef typename Frag<E>::type frag;
@@ -269,21 +332,25 @@ __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& c
     const gcptr a = an, b = bn;
     ch.fetch(r + 1, an, bn);
     GM const unsigned short* ap = (GM const unsigned short*)a;
-    GM const unsigned short* bp = (GM const unsigned short*)b + (long long)min(j, g.n - 1) * g.ldb;
-    const bool b_vec = (T == 32) ? ch.b_vec16(b) : ch.b_vec8(b);
-    const bool a_vec = g.vnni_a && ch.a_vec4(a);
+    if constexpr (TA) ap += (long long)il * g.lda;             // the lane's row
+    GM const unsigned short* bp = (GM const unsigned short*)b + lane_index<!TB>(min(j, g.n - 1), g.ldb);
+    bool b_vec = false, a_vec;
+    if constexpr (!TB) b_vec = (T == 32) ? ch.b_vec16(b) : ch.b_vec8(b);
+    if constexpr (TA) a_vec = (T == 32) ? ch.a_vec16(a) : ch.a_vec8(a); else a_vec = g.vnni_a && ch.a_vec4(a);
     int kk = 0;
-    if constexpr (DEEP) {                      // segments: 64 k per round of requests when both operands take the wide loads (32 more registers)
-      if (a_vec && b_vec) for (; kk < kbig; kk += 4 * KS) steps_bf16<T, 4, true>(g, acc, ap, bp, kk, il, h, true, true);
+    if constexpr (DEEP && !TB) {               // segments: 64 k per round of requests when both operands take the wide loads (32 more registers)
+      if (a_vec && b_vec) for (; kk < kbig; kk += 4 * KS) steps_bf16<T, 4, true, TA, TB>(g, acc, ap, bp, kk, il, h, true, true);
     }
-    for (; kk < kfull; kk += KS) steps_bf16<T, 1, false>(g, acc, ap, bp, kk, il, h, a_vec, b_vec);
+    for (; kk < kfull; kk += KS) steps_bf16<T, 1, false, TA, TB>(g, acc, ap, bp, kk, il, h, a_vec, b_vec);
     if (kk < K) {                              // ragged k: A = -0 (0x8000), B = +0 beyond K
       const int k0 = kk + E * h;
       frag x, y;
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int kx = k0 + e, kc = min(kx, K - 1);
-        const unsigned short vb = bp[kc], va = a_bf16(g, ap, il, kc);
+        unsigned short vb, va;
+        if constexpr (TB) vb = bp[kc * g.ldb]; else vb = bp[kc];
+        if constexpr (TA) va = ap[kc]; else va = a_bf16(g, ap, il, kc);
         x[e] = (short)(kx < K ? vb : 0);
         y[e] = (short)(kx < K ? va : 0x8000);
       }
@@ -296,16 +363,16 @@ __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& c
 // f64, one 16 x 16 tile: lane (g = lane % 16, s = lane / 16) feeds A(i0 + g, k0 + s) and B(k0 + s, j0 + g) per MFMA and holds C(i0 + g, j0 + s + 4 r) in
 // register pair r (the f64 instruction's own map, gemm_f64_kernels.hip).  Same clamping and padding as the f32 tile; k advances in blocks of 32, then 16, then one
 // block of up to four ragged steps, every request of a block in flight before its MFMAs.
-template <int U> __device__ __forceinline__ void steps_f64(f64x4& acc, GM const double* ap, GM const double* bp, int kk, int lda, int s) {
+template <int U, bool TA = false, bool TB = false> __device__ __forceinline__ void steps_f64(f64x4& acc, GM const double* ap, GM const double* bp, int kk, int lda, int s, int ldb = 0) {
   double av[U], bv[U];
 #pragma unroll
-  for (int e = 0; e < U; ++e) av[e] = ap[(kk + 4 * e + s) * lda];
+  for (int e = 0; e < U; ++e) av[e] = ap[k_index<TA>(kk + 4 * e + s, lda)];
 #pragma unroll
-  for (int e = 0; e < U; ++e) bv[e] = bp[kk + 4 * e + s];
+  for (int e = 0; e < U; ++e) bv[e] = bp[k_index<!TB>(kk + 4 * e + s, ldb)];
 #pragma unroll
   for (int e = 0; e < U; ++e) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[e], av[e], acc, 0, 0, 0);
 }
-template <typename Chain> __device__ __forceinline__ void tile_f64(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
+template <typename Chain, bool TA = false, bool TB = false> __device__ __forceinline__ void tile_f64(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
   const int lr = (int)(lane & 15u), s = (int)(lane >> 4);
   const int i = i0 + lr, j = j0 + lr;
   const bool mv = i < g.m;
@@ -314,24 +381,24 @@ template <typename Chain> __device__ __forceinline__ void tile_f64(const GemmGro
     const int jc = j0 + s + 4 * r.value;
     acc[r.value] = (g.beta1 && mv && jc < g.n) ? ((GM const double*)c)[(long long)jc * g.ldc + i] : 0.0;
   });
-  const int K = g.k, lda = g.lda;
+  const int K = g.k, lda = g.lda, ldb = g.ldb;
   const int kbig = K - K % 32, kfull = K - K % 16;
   gcptr an = nullptr, bn = nullptr;
   if (ch.count) ch.fetch(0, an, bn);
   for (unsigned long long r = 0; r < ch.count; ++r) {
     const gcptr a = an, b = bn;
     ch.fetch(r + 1, an, bn);
-    GM const double* ap = (GM const double*)a + min(i, g.m - 1);
-    GM const double* bp = (GM const double*)b + (long long)min(j, g.n - 1) * g.ldb;
+    GM const double* ap = (GM const double*)a + lane_index<TA>(min(i, g.m - 1), lda);
+    GM const double* bp = (GM const double*)b + lane_index<!TB>(min(j, g.n - 1), g.ldb);
     int kk = 0;
-    for (; kk < kbig; kk += 32) steps_f64<8>(acc, ap, bp, kk, lda, s);
-    for (; kk < kfull; kk += 16) steps_f64<4>(acc, ap, bp, kk, lda, s);
+    for (; kk < kbig; kk += 32) steps_f64<8, TA, TB>(acc, ap, bp, kk, lda, s, ldb);
+    for (; kk < kfull; kk += 16) steps_f64<4, TA, TB>(acc, ap, bp, kk, lda, s, ldb);
     if (kk < K) {                              // ragged k, up to four steps: A = -0, B = +0 beyond K
       double av[4], bv[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int kx = kk + 4 * e + s, kc = min(kx, K - 1);
-        const double va = ap[kc * lda], vb = bp[kc];
+        const double va = ap[k_index<TA>(kc, lda)], vb = bp[k_index<!TB>(kc, ldb)];
         av[e] = kx < K ? va : -0.0; bv[e] = kx < K ? vb : 0.0;
       }
 #pragma unroll

@@ -310,6 +310,11 @@ const char* gemm_segments_kernel_name(int cls);
 int launch_gemm_segments_fused(const GemmGroupDesc& g, const GemmSegEpilogue& e, int cls, unsigned long long items, const unsigned long long* seg_ptr,
   const void* const* a_list, const void* const* b_list, void* const* c_list, void* stream);
 const char* gemm_segments_fused_kernel_name(int cls);
+// libxsmm_hip_gemm_batch_reduce_segments_offsets: g.a / g.b / g.c are the three bases; forms: bit 0 TRANS_A, bit 1 TRANS_B, bit 2 / 3: lda spans a multiple of 16 / 8 bytes
+// (the wide loads of a transposed A)
+int launch_gemm_segments_offs(const GemmGroupDesc& g, int forms, int cls, unsigned long long items, const unsigned long long* seg_ptr, const long long* a_offs,
+  const long long* b_offs, const long long* c_offs, void* stream);
+const char* gemm_segments_offs_kernel_name(int cls, int forms);
 int launch_spmm(const SpmmArgs& args, void* stream, const char** kernel_name);
 int launch_bcsc(const BcscArgs& args, void* stream, const char** kernel_name);
 // Automatic streaming decision (libxsmm_hip_set_streaming_hint(0)): a launch whose own operands exceed the Infinity Cache streams -- and so does a launch whose operands

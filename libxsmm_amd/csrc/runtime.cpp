@@ -2331,13 +2331,22 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* gr
 // ---- segments (libxsmm_hip_gemm_batch_reduce_segments): ADDRESS batch-reduce with a count per C block, one launch -------------------------------------
 // The count is the one argument of a BRGEMM call that the reference re-reads on every call [ref: gemm ref :490-492]; here it is seg_ptr[s + 1] - seg_ptr[s].
 // Nothing is staged or uploaded: the four arrays are read on the device as they are, the shape travels in the kernel arguments, so the call can be captured.
-// What both segments entries ask of their arguments and their handle, in one place: every refusal is set here, before anything is launched.  `ext` is the
-// entry (libxsmm_hip_gemm_ext_batch_reduce_segments takes ext handles and only those); on success `g` holds the shape as the kernels read it, `cls` the
-// kernel class (0 f32, 1 bf16, 2 f64) and `tiles` the C tiles of one segment.
+// What the three segments entries ask of their arguments and their handle, in one place: every refusal is set here, before anything is launched.  `ext` is the
+// entry (libxsmm_hip_gemm_ext_batch_reduce_segments takes ext handles and only those); `forms` != NULL is libxsmm_hip_gemm_batch_reduce_segments_offsets, which
+// takes OFFSET handles, three bases in param's primary slots (the lists are then a_offs / b_offs / c_offs) and transposed operands: *forms receives the bits
+// its kernels read.  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64) and `tiles` the C tiles of one segment.
 static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, const unsigned long long* seg_ptr,
-  const void* const* a_list, const void* const* b_list, void* const* c_list, GemmGroupDesc& g, int& cls, unsigned long long& tiles) {
+  const void* a_list, const void* b_list, const void* c_list, GemmGroupDesc& g, int& cls, unsigned long long& tiles, int* forms = nullptr) {
+  const bool offsets = forms != nullptr;
   if (!param || !seg_ptr || !a_list || !b_list || !c_list) {
-    set_error(-2, "%s: %s is NULL but nsegments = %zu", fn, !param ? "param" : (!seg_ptr ? "seg_ptr" : (!a_list ? "a_list" : (!b_list ? "b_list" : "c_list"))), nsegments); return nullptr;
+    set_error(-2, "%s: %s is NULL but nsegments = %zu", fn, !param ? "param" : (!seg_ptr ? "seg_ptr" : (!a_list ? (offsets ? "a_offs" : "a_list") : (!b_list ? (offsets ? "b_offs" : "b_list") :
+      (offsets ? "c_offs" : "c_list")))), nsegments); return nullptr;
+  }
+  if (offsets) {
+    const libxsmm_gemm_param* q = (const libxsmm_gemm_param*)param;
+    if (!q->a.primary || !q->b.primary || !q->c.primary) {
+      set_error(-2, "%s: param->%s.primary (the base the offsets are added to) is NULL but nsegments = %zu", fn, !q->a.primary ? "a" : (!q->b.primary ? "b" : "c"), nsegments); return nullptr;
+    }
   }
   KernelCtx* k = ctx_from_handle(kernel);
   if (!k) { set_error(-3, "%s: unknown kernel handle", fn); return nullptr; }
@@ -2346,7 +2355,10 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
   const bool is_ext = (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI) != 0;
   if (!ext && is_ext) { set_error(-3, "%s: ext handles are not taken", fn); return nullptr; }
   if (ext && !is_ext) { set_error(-3, "%s: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_reduce_segments)", fn); return nullptr; }
-  if (!(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS)) {
+  if (offsets && !(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET)) {
+    set_error(-3, "%s: handle is not an OFFSET batch-reduce kernel (libxsmm_dispatch_brgemm with LIBXSMM_GEMM_BATCH_REDUCE_OFFSET)", fn); return nullptr;
+  }
+  if (!offsets && !(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS)) {
     set_error(-3, "%s: handle is not an ADDRESS batch-reduce kernel (%s with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS)", fn, ext ? "libxsmm_dispatch_brgemm_ext" : "libxsmm_dispatch_brgemm"); return nullptr;
   }
   const bool f32 = d.a_type == LIBXSMM_DATATYPE_F32 && d.b_type == LIBXSMM_DATATYPE_F32 && d.c_type == LIBXSMM_DATATYPE_F32;
@@ -2356,15 +2368,21 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
     set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return nullptr;
   }
   const unsigned int f = effective_gemm_flags(d);
-  if (f & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return nullptr; }
+  const bool ta = (f & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (f & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
+  if (!offsets && (ta || tb)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return nullptr; }
   if (f & (LIBXSMM_GEMM_FLAG_VNNI_B | LIBXSMM_GEMM_FLAG_VNNI_C)) { set_error(-3, "%s: VNNI layouts of B and C are not taken (A flat or VNNI-2, B and C flat)", fn); return nullptr; }
+  if (ta && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) { set_error(-3, "%s: a VNNI-2 A is not taken together with TRANS_A (a transposed A is flat)", fn); return nullptr; }
   const unsigned int allowed = LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_ALIGN_A | LIBXSMM_GEMM_FLAG_ALIGN_C_NTS_HINT | LIBXSMM_GEMM_FLAG_NO_RESET_TILECONFIG |
-    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS |
+    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI |
+    (offsets ? (unsigned int)(LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B) : (unsigned int)LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS) |
     (ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
-  if (f & ~allowed) { set_error(-3, "%s: flags 0x%x are not taken (beta, VNNI_A and the hints only)", fn, f & ~allowed); return nullptr; }
-  // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers): the grouped kernels' bound
+  if (f & ~allowed) {
+    set_error(-3, offsets ? "%s: flags 0x%x are not taken (beta, VNNI_A, TRANS_A, TRANS_B and the hints only)" : "%s: flags 0x%x are not taken (beta, VNNI_A and the hints only)", fn, f & ~allowed);
+    return nullptr;
+  }
+  // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers): the grouped kernels' bound; a transposed operand spans lda x m / ldb x k
   const unsigned long long lim = 1ull << 31;
-  if ((unsigned long long)d.lda * (d.k + 1) >= lim || (unsigned long long)d.ldb * d.n >= lim || (unsigned long long)d.ldc * d.n >= lim) {
+  if ((unsigned long long)d.lda * (ta ? d.m : d.k + 1) >= lim || (unsigned long long)d.ldb * (tb ? d.k : d.n) >= lim || (unsigned long long)d.ldc * d.n >= lim) {
     set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return nullptr;
   }
   cls = f64 ? 2 : (bf16 ? 1 : 0);
@@ -2376,8 +2394,14 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
   g.vnni_a = (bf16 && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
   g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
   // what the leading dimension allows of the wider loads; the block pointers are tested per product on the device
-  const unsigned long long colb = (unsigned long long)d.ldb * (bf16 ? 2 : (f64 ? 8 : 4));
-  g.a_vec4 = bf16 ? 1 : 0; g.b_vec16 = (colb & 15) == 0 ? 1 : 0; g.b_vec8 = (colb & 7) == 0 ? 1 : 0;
+  const unsigned long long esz = bf16 ? 2 : (f64 ? 8 : 4), colb = (unsigned long long)d.ldb * esz;
+  g.a_vec4 = bf16 ? 1 : 0; g.b_vec16 = (!tb && (colb & 15) == 0) ? 1 : 0; g.b_vec8 = (!tb && (colb & 7) == 0) ? 1 : 0;
+  if (offsets) {
+    const libxsmm_gemm_param* q = (const libxsmm_gemm_param*)param;
+    g.a = (const char*)q->a.primary; g.b = (const char*)q->b.primary; g.c = (char*)q->c.primary;
+    const unsigned long long rowb = (unsigned long long)d.lda * esz;          // a transposed A: the k run of a row takes B's wide loads
+    *forms = (ta ? 1 : 0) | (tb ? 2 : 0) | ((ta && (rowb & 15) == 0) ? 4 : 0) | ((ta && (rowb & 7) == 0) ? 8 : 0);
+  }
   tiles = (unsigned long long)g.tiles_m * (unsigned long long)g.tiles_n;
   if (tiles != 0 && (unsigned long long)nsegments > ~0ull / tiles - 4) { set_error(-3, "%s: nsegments x C tiles overflows 64 bits", fn); return nullptr; }
   return k;
@@ -2387,7 +2411,7 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction ker
   static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments";
   if (nsegments == 0) return;
   GemmGroupDesc g; int cls = 0; unsigned long long tiles = 0;
-  KernelCtx* k = segments_validate(fn, false, (const void*)kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, g, cls, tiles);
+  KernelCtx* k = segments_validate(fn, false, (const void*)kernel, param, nsegments, seg_ptr, (const void*)a_list, (const void*)b_list, (const void*)c_list, g, cls, tiles);
   if (!k) return;
   coalesce_flush();
   if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
@@ -2406,7 +2430,7 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction
   static const char* const fn = "libxsmm_hip_gemm_ext_batch_reduce_segments";
   if (nsegments == 0) return;
   GemmGroupDesc g; int cls = 0; unsigned long long tiles = 0;
-  KernelCtx* k = segments_validate(fn, true, (const void*)kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, g, cls, tiles);
+  KernelCtx* k = segments_validate(fn, true, (const void*)kernel, param, nsegments, seg_ptr, (const void*)a_list, (const void*)b_list, (const void*)c_list, g, cls, tiles);
   if (!k) return;
   const libxsmm_gemm_descriptor& d = k->g;
   GemmSegEpilogue e;
@@ -2437,6 +2461,24 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction
   const char* kname = fused ? gemm_segments_fused_kernel_name(cls) : gemm_segments_kernel_name(cls);
   const int err = fused ? launch_gemm_segments_fused(g, e, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream)
                         : launch_gemm_segments(g, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream);
+  k->kname_batched = kname;
+  finish_launch(err, kname);
+}
+// Segments through OFFSET batch-reduce handles [ref: gemm ref :509-513, :186-188]: three bases by value, signed byte offsets in the lists -- a pattern's lists are
+// computed once and serve every buffer the bases point at -- and transposed operands, the backward passes of a block-sparse layer (gemm_segments_kernels.hip).
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
+  const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs) {
+  static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments_offsets";
+  if (nsegments == 0) return;
+  GemmGroupDesc g; int cls = 0, forms = 0; unsigned long long tiles = 0;
+  KernelCtx* k = segments_validate(fn, false, (const void*)kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, g, cls, tiles, &forms);
+  if (!k) return;
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  if (tiles == 0) return;                               // m or n is 0: no C
+  const char* kname = gemm_segments_offs_kernel_name(cls, forms);
+  const int err = launch_gemm_segments_offs(g, forms, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_offs, b_offs, c_offs, tls().stream);
   k->kname_batched = kname;
   finish_launch(err, kname);
 }
