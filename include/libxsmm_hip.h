@@ -284,11 +284,48 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction
  * section.  Errors are set before anything is launched, one per refusal.  -2: param, seg_ptr, a_offs, b_offs, c_offs or one of the three bases is NULL while
  * nsegments > 0; -3: an unknown handle, a TPP / equation / sparse / ext handle, a GEMM handle that is not OFFSET batch-reduce, or a type, layout or flag
  * outside the list above (the message names which); -4: no device.  nsegments = 0 does nothing.  libxsmm_hip_kernel_name(kernel, 1) names the kernel that
- * ran (gemm_segments_offs_f32_kernel<ta,tb>, _f64_kernel<ta,tb>, _bf16_kernel<ta,tb>: one instance per pair of transposes).  The two ADDRESS entries above keep refusing transposed operands; the fused (ext) form
- * has no OFFSET entry.
+ * ran (gemm_segments_offs_f32_kernel<ta,tb>, _f64_kernel<ta,tb>, _bf16_kernel<ta,tb>: one instance per pair of transposes).  The two ADDRESS entries above keep refusing transposed operands; ext handles go to
+ * libxsmm_hip_gemm_ext_batch_reduce_segments_offsets below.
  */
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
   size_t nsegments, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs);
+
+/* OFFSET segments through an ext handle (libxsmm_dispatch_brgemm_ext with LIBXSMM_GEMM_BATCH_REDUCE_OFFSET): the call a convolution or a block-sparse layer in
+ * the reference's style makes -- offset lists computed once per layer geometry, bias and activation fused -- with a count of its own per C block, as ONE launch
+ * [ref: src/generator_gemm_reference_impl.c:509-513, :186-188 for the offsets, src/generator_gemm_reference_impl.c:294-372 for the epilogue]:
+ *   libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, d_offs, mask_offs)
+ *     ==  for (s = 0; s < nsegments; ++s) { q = *param; cnt = seg_ptr[s+1] - seg_ptr[s];
+ *           q.a.secondary = (void*)(a_offs + seg_ptr[s]);  q.b.secondary = (void*)(b_offs + seg_ptr[s]);
+ *           q.c.primary   = (char*)param->c.primary + c_offs[s];
+ *           q.d.primary   = (char*)param->d.primary + (d_offs ? d_offs[s] : 0);
+ *           q.c.secondary = mask_offs ? (char*)param->c.secondary + mask_offs[s] : NULL;
+ *           q.op.tertiary = &cnt;  kernel(&q); }
+ * Five bases, all device-accessible and passed BY VALUE in the kernel arguments: param->a.primary, b.primary and c.primary as in
+ * libxsmm_hip_gemm_batch_reduce_segments_offsets; param->d.primary, the bias base, needed only when the handle has a column bias; param->c.secondary, the mask
+ * base, needed only with LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT.  seg_ptr, a_offs, b_offs and c_offs are those of the plain offsets entry.  d_offs and
+ * mask_offs hold nsegments signed byte offsets each: d_offs[s] leads to the m-vector bias of C's type (entries may repeat; element alignment only), and
+ * d_offs == NULL on a bias handle means that the one bias at param->d.primary serves every segment; mask_offs[s] leads to a ReLU bitmask block of
+ * ((ldc + 15) / 16) * 16 / 8 * n bytes, is required exactly when the handle's ReLU carries the bitmask flag and is ignored otherwise.  Every list is read in
+ * place on the device: nothing is staged, the call may be captured, and a captured call replays on the same five bases.  Overlapping C blocks or overlapping
+ * mask blocks are undefined; A, B and bias blocks may be shared freely.
+ * Per segment, as in libxsmm_hip_gemm_ext_batch_reduce_segments: the accumulator starts at bias[i] (beta = 0), at bias[i] + C(i,j) (beta = 1, one f32 add), or
+ * at C(i,j) / +0 without a bias; one chain over (product, k) in list order -- for f32 the k-ordered fmaf chain bit for bit in all four forms; mask bit i % 8 of
+ * byte i / 8 + j * (mask_ld / 8) is !(x <= 0) of the sum and is written for i < m, j < n only -- every other bit and byte of the mask block stays the caller's;
+ * then the activation; then one rounding for a bf16 C.  A segment of count 0 stores the activation of its start value (the bias, bias + C, C or +0) and the
+ * mask taken from it.  Work is handed out in list order; a segment is never split.
+ * Eligible handles: every handle the plain offsets entry takes, made into an ext handle -- f32 -> f32, bf16 -> f32 / bf16; A flat, TRANS_A or (bf16, without
+ * TRANS_A) VNNI-2; B flat or TRANS_B; NN, TN, NT and TT; beta 0 or 1; the hints; element offsets below 2^31 -- with BINARY_ADD + BCAST_COL_IN_0/1, cp RELU (with
+ * or without bitmask), cp SIGMOID, or no operator at all: an ext handle without operators is taken for f64 as well and runs the plain offsets kernels; f64 with
+ * operators is refused.  Errors are set before anything is launched, one per refusal.  -2: param, seg_ptr, a_offs, b_offs, c_offs or one of the three bases is
+ * NULL while nsegments > 0; a bias handle with param->d.primary NULL; a bitmask handle with mask_offs or param->c.secondary NULL.  -3: an unknown handle, a
+ * non-ext / TPP / equation / sparse handle, a handle that is not OFFSET batch-reduce, a type, layout, flag or operator outside the list (the message names
+ * which).  -4: no device.  nsegments = 0 does nothing.  Follows the thread's launch mode like its siblings: blocking, stream-ordered, coalescing (the queue is
+ * flushed first), inside a pipeline section.  libxsmm_hip_kernel_name(kernel, 1) names the kernel that ran (gemm_segments_offs_f32_fused_kernel<ta,tb>,
+ * gemm_segments_offs_bf16_fused_kernel<ta,tb>; without operators the plain offsets entry's kernels).
+ */
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param,
+  size_t nsegments, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs,
+  const long long* d_offs, const long long* mask_offs);
 
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns

@@ -128,6 +128,14 @@ struct GemmSegEpilogue {
   void* const* mask_list;                           // one ReLU bitmask block per segment (act == 2)
   int colbias, act, mask_ld;                        // act: 0 none, 1 ReLU, 2 ReLU + bitmask, 3 sigmoid; mask_ld = ldc rounded up to 16
 };
+// libxsmm_hip_gemm_ext_batch_reduce_segments_offsets: the same epilogue whose blocks lie at a base plus a signed byte offset per segment
+struct GemmSegOffsEpilogue {
+  const char* d; char* mask;                        // the bias base (param->d.primary) and the mask base (param->c.secondary)
+  const long long* d_offs;                          // one byte offset per segment, or NULL: `d` is shared by every segment
+  const long long* mask_offs;                       // one byte offset per segment (act == 2)
+  int colbias, act, mask_ld;                        // as in GemmSegEpilogue
+  int a_wide;                                       // bit 0 / 1: the rows of a transposed A are multiples of 16 / 8 bytes apart (OffsetChain::va16 / va8)
+};
 
 // sparse operator S (rows x inner) applied to a packed panel:
 //   Y[r][q] (+)= sum_z val[z] * X[idx[z]][q],   q = 0..ncols-1 contiguous, for `nouter` slabs
@@ -315,6 +323,11 @@ const char* gemm_segments_fused_kernel_name(int cls);
 int launch_gemm_segments_offs(const GemmGroupDesc& g, int forms, int cls, unsigned long long items, const unsigned long long* seg_ptr, const long long* a_offs,
   const long long* b_offs, const long long* c_offs, void* stream);
 const char* gemm_segments_offs_kernel_name(int cls, int forms);
+// gemm_segments_offs_fused_kernels.hip (libxsmm_hip_gemm_ext_batch_reduce_segments_offsets): the offsets launch with the fused epilogue; cls 0 or 1, forms bit 0 / 1 as
+// above (bits 2 / 3 travel in e.a_wide)
+int launch_gemm_segments_offs_fused(const GemmGroupDesc& g, const GemmSegOffsEpilogue& e, int forms, int cls, unsigned long long items, const unsigned long long* seg_ptr,
+  const long long* a_offs, const long long* b_offs, const long long* c_offs, void* stream);
+const char* gemm_segments_offs_fused_kernel_name(int cls, int forms);
 int launch_spmm(const SpmmArgs& args, void* stream, const char** kernel_name);
 int launch_bcsc(const BcscArgs& args, void* stream, const char** kernel_name);
 // Automatic streaming decision (libxsmm_hip_set_streaming_hint(0)): a launch whose own operands exceed the Infinity Cache streams -- and so does a launch whose operands

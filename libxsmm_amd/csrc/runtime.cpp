@@ -2331,10 +2331,10 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* gr
 // ---- segments (libxsmm_hip_gemm_batch_reduce_segments): ADDRESS batch-reduce with a count per C block, one launch -------------------------------------
 // The count is the one argument of a BRGEMM call that the reference re-reads on every call [ref: gemm ref :490-492]; here it is seg_ptr[s + 1] - seg_ptr[s].
 // Nothing is staged or uploaded: the four arrays are read on the device as they are, the shape travels in the kernel arguments, so the call can be captured.
-// What the three segments entries ask of their arguments and their handle, in one place: every refusal is set here, before anything is launched.  `ext` is the
-// entry (libxsmm_hip_gemm_ext_batch_reduce_segments takes ext handles and only those); `forms` != NULL is libxsmm_hip_gemm_batch_reduce_segments_offsets, which
-// takes OFFSET handles, three bases in param's primary slots (the lists are then a_offs / b_offs / c_offs) and transposed operands: *forms receives the bits
-// its kernels read.  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64) and `tiles` the C tiles of one segment.
+// What the four segments entries ask of their arguments and their handle, in one place: every refusal is set here, before anything is launched.  `ext` is the
+// entry (the two libxsmm_hip_gemm_ext_batch_reduce_segments* entries take ext handles and only those); `forms` != NULL is one of the two *_offsets entries, which
+// take OFFSET handles, three bases in param's primary slots (the lists are then a_offs / b_offs / c_offs) and transposed operands: *forms receives the bits
+// their kernels read.  (a, b and c sit at the same place in libxsmm_gemm_param and libxsmm_gemm_ext_param.)  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64) and `tiles` the C tiles of one segment.
 static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, const unsigned long long* seg_ptr,
   const void* a_list, const void* b_list, const void* c_list, GemmGroupDesc& g, int& cls, unsigned long long& tiles, int* forms = nullptr) {
   const bool offsets = forms != nullptr;
@@ -2354,9 +2354,11 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
   const libxsmm_gemm_descriptor& d = k->g;
   const bool is_ext = (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI) != 0;
   if (!ext && is_ext) { set_error(-3, "%s: ext handles are not taken", fn); return nullptr; }
-  if (ext && !is_ext) { set_error(-3, "%s: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_reduce_segments)", fn); return nullptr; }
+  if (ext && !is_ext) {
+    set_error(-3, "%s: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_reduce_segments%s)", fn, offsets ? "_offsets" : ""); return nullptr;
+  }
   if (offsets && !(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET)) {
-    set_error(-3, "%s: handle is not an OFFSET batch-reduce kernel (libxsmm_dispatch_brgemm with LIBXSMM_GEMM_BATCH_REDUCE_OFFSET)", fn); return nullptr;
+    set_error(-3, "%s: handle is not an OFFSET batch-reduce kernel (%s with LIBXSMM_GEMM_BATCH_REDUCE_OFFSET)", fn, ext ? "libxsmm_dispatch_brgemm_ext" : "libxsmm_dispatch_brgemm"); return nullptr;
   }
   if (!offsets && !(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS)) {
     set_error(-3, "%s: handle is not an ADDRESS batch-reduce kernel (%s with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS)", fn, ext ? "libxsmm_dispatch_brgemm_ext" : "libxsmm_dispatch_brgemm"); return nullptr;
@@ -2406,6 +2408,20 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
   if (tiles != 0 && (unsigned long long)nsegments > ~0ull / tiles - 4) { set_error(-3, "%s: nsegments x C tiles overflows 64 bits", fn); return nullptr; }
   return k;
 }
+// The operators of an ext handle as the fused segment kernels take them, decoded as run_gemm decodes them: colbias, and act 0 none, 1 ReLU, 2 ReLU + bitmask,
+// 3 sigmoid.  false (the error is set) for every other operator and for f64 with any.
+static bool segments_operators(const char* fn, const libxsmm_gemm_descriptor& d, int cls, int& colbias_out, int& act) {
+  const bool colbias = d.bin_type == LIBXSMM_MELTW_TYPE_BINARY_ADD && (d.bin_flags & (LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_0 | LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_1));
+  if ((d.bin_type != LIBXSMM_MELTW_TYPE_BINARY_NONE && !colbias) || d.ap_type != 0 || d.bp_type != 0 ||
+      (d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_NONE && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_RELU && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_SIGMOID)) {
+    set_error(-3, "%s: fused operator not taken (column-broadcast BINARY_ADD, cp RELU with or without bitmask, cp SIGMOID only)", fn); return false;
+  }
+  colbias_out = colbias ? 1 : 0; act = 0;
+  if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_RELU) act = (d.cp_flags & LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT) ? 2 : 1;
+  else if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_SIGMOID) act = 3;
+  if (cls == 2 && (colbias || act != 0)) { set_error(-3, "%s: f64 ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
+  return true;
+}
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
   const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list) {
   static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments";
@@ -2435,16 +2451,8 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction
   const libxsmm_gemm_descriptor& d = k->g;
   GemmSegEpilogue e;
   std::memset(&e, 0, sizeof(e));
-  const bool colbias = d.bin_type == LIBXSMM_MELTW_TYPE_BINARY_ADD && (d.bin_flags & (LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_0 | LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_1));
-  if ((d.bin_type != LIBXSMM_MELTW_TYPE_BINARY_NONE && !colbias) || d.ap_type != 0 || d.bp_type != 0 ||
-      (d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_NONE && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_RELU && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_SIGMOID)) {
-    set_error(-3, "%s: fused operator not taken (column-broadcast BINARY_ADD, cp RELU with or without bitmask, cp SIGMOID only)", fn); return;
-  }
-  e.colbias = colbias ? 1 : 0;
-  if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_RELU) e.act = (d.cp_flags & LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT) ? 2 : 1;
-  else if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_SIGMOID) e.act = 3;
+  if (!segments_operators(fn, d, cls, e.colbias, e.act)) return;
   const bool fused = e.colbias != 0 || e.act != 0;
-  if (cls == 2 && fused) { set_error(-3, "%s: f64 ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return; }
   if (e.colbias) {
     e.d_list = d_list; e.d = (const char*)param->d.primary;
     if (!d_list && !e.d) { set_error(-2, "%s: fused column bias requested but d_list and param->d.primary are both NULL", fn); return; }
@@ -2479,6 +2487,42 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunc
   if (tiles == 0) return;                               // m or n is 0: no C
   const char* kname = gemm_segments_offs_kernel_name(cls, forms);
   const int err = launch_gemm_segments_offs(g, forms, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_offs, b_offs, c_offs, tls().stream);
+  k->kname_batched = kname;
+  finish_launch(err, kname);
+}
+// The fourth corner: OFFSET segments through an ext handle [ref: gemm ref :294-372, :509-513].  Five bases by value -- A, B, C, the bias base (d.primary) and
+// the mask base (c.secondary) -- and two more offset lists; the operators are those of libxsmm_hip_gemm_ext_batch_reduce_segments, decoded in one place
+// (segments_operators).  Nothing is staged, so this call, too, can be captured (gemm_segments_offs_fused_kernels.hip).
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param, size_t nsegments,
+  const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs, const long long* d_offs, const long long* mask_offs) {
+  static const char* const fn = "libxsmm_hip_gemm_ext_batch_reduce_segments_offsets";
+  if (nsegments == 0) return;
+  GemmGroupDesc g; int cls = 0, forms = 0; unsigned long long tiles = 0;
+  KernelCtx* k = segments_validate(fn, true, (const void*)kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, g, cls, tiles, &forms);
+  if (!k) return;
+  const libxsmm_gemm_descriptor& d = k->g;
+  GemmSegOffsEpilogue e;
+  std::memset(&e, 0, sizeof(e));
+  if (!segments_operators(fn, d, cls, e.colbias, e.act)) return;
+  const bool fused = e.colbias != 0 || e.act != 0;
+  if (e.colbias) {
+    e.d = (const char*)param->d.primary; e.d_offs = d_offs;
+    if (!e.d) { set_error(-2, "%s: fused column bias requested but param->d.primary (the base d_offs is added to; the shared bias without d_offs) is NULL", fn); return; }
+  }
+  if (e.act == 2) {
+    e.mask = (char*)param->c.secondary; e.mask_offs = mask_offs; e.mask_ld = ((int)d.ldc + 15) / 16 * 16;
+    if (!mask_offs) { set_error(-2, "%s: ReLU bitmask requested but mask_offs is NULL", fn); return; }
+    if (!e.mask) { set_error(-2, "%s: ReLU bitmask requested but param->c.secondary (the base mask_offs is added to) is NULL", fn); return; }
+  }
+  e.a_wide = (forms >> 2) & 3;
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  if (tiles == 0) return;                               // m or n is 0: no C
+  // an ext handle without operators is the plain product: it runs the plain offsets kernels (f64 among them)
+  const char* kname = fused ? gemm_segments_offs_fused_kernel_name(cls, forms) : gemm_segments_offs_kernel_name(cls, forms);
+  const int err = fused ? launch_gemm_segments_offs_fused(g, e, forms, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_offs, b_offs, c_offs, tls().stream)
+                        : launch_gemm_segments_offs(g, forms, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_offs, b_offs, c_offs, tls().stream);
   k->kname_batched = kname;
   finish_launch(err, kname);
 }
