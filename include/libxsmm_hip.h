@@ -92,6 +92,19 @@ LIBXSMM_API void libxsmm_hip_sync(void);
  * libxsmm_hip_sync and libxsmm_hip_set_stream close an open section.  Each lane has its own partial-result workspace. */
 LIBXSMM_API int libxsmm_hip_pipeline_begin(int lanes);
 LIBXSMM_API int libxsmm_hip_pipeline_end(void);
+/** Capture-time fusion.  While a stream is being captured into a hipGraph, consecutive strided-batch launches of the lean f32 kernel (32 x 32 problems, 16-byte
+ * aligned C, non-negative 32-bit batch strides) through ONE handle with the same count, strides and batch-reduce count are folded into one kernel node when
+ * the new launch is address-independent of every launch already in the node: its C range meets none of their A, B or C ranges and their C ranges meet neither
+ * its A nor its B range (bounding intervals base ... base + (count - 1) * stride + extent; ranges that only touch are independent).  The graph stays a linear
+ * chain with fewer, larger kernel nodes; results are bit for bit those of the separate launches.  What the caller can see: an event recorded between two fused
+ * launches completes after both.  Anything else on the stream between two launches (another kernel, a copy, a wait on another stream) ends the run, as does a
+ * pipeline section.  Nothing changes outside a capture.
+ * max_launches: the most launches one node may hold; 0 or 1 = off; values above the built-in limit (16) are lowered to it.  Returns the previous value.
+ * Process-wide, on by default; LIBXSMM_HIP_CAPTURE_FUSION=0 starts with it off (any other number presets max_launches).  If a graph call fails the launch is
+ * issued on its own, fusion switches itself off for the process and the thread's error state says why. */
+LIBXSMM_API int libxsmm_hip_set_capture_fusion(int max_launches);
+/** Number of calls of the calling thread since the last reset that were folded into the node of a launch before them (libxsmm_hip_launch_count counts them too). */
+LIBXSMM_API unsigned long long libxsmm_hip_fused_launch_count(int reset);
 /** Sticky error state of the calling thread (0 = none); kernels have no error channel. */
 LIBXSMM_API int libxsmm_hip_get_last_error(void);
 LIBXSMM_API const char* libxsmm_hip_get_last_error_string(void);

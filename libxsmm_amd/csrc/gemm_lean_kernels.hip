@@ -46,10 +46,11 @@ template <int AUX> __device__ __forceinline__ f32x4 ld16_pol(__amdgpu_buffer_rsr
 // POL 3 (round 4): POL 1's nt loads with POL 0's 16-byte stores through the LDS image -- tools/headline_probe: a copy of this footprint with nt loads and
 //        16-byte nt stores takes 8.99 us where the POL 1 kernel takes 9.99 (dword stores: four times the store instructions).  The stores are sc1, not nt
 //        (above).  POL 0 keeps its nt stores: with cacheable operands the sc1 form is slower from HBM (tools/policy_probe gemm mode: 10.84 vs 9.85 us).
+// The kernel's body: the launch whose problem bases are pa / pb / pc (the whole kernel of a single launch; one blockIdx.y slice of a fused one, below)
 template <bool TA, bool TB, bool SINGLE, int POL, typename S>
-__global__ __launch_bounds__(256) void gemm_f32_stream_kernel_lean(const char* pa, const char* pb, char* pc, S bs_a, S bs_b, S bs_c, unsigned int nbatch,
-                                                                   unsigned int lda, unsigned int ldb, unsigned int ldc,
-                                                                   unsigned int nchunks, unsigned int kchunks, long long brs_a, long long brs_b) {
+__device__ __forceinline__ void lean_launch_body(const char* pa, const char* pb, char* pc, S bs_a, S bs_b, S bs_c, unsigned int nbatch,
+                                                 unsigned int lda, unsigned int ldb, unsigned int ldc,
+                                                 unsigned int nchunks, unsigned int kchunks, long long brs_a, long long brs_b) {
   constexpr int AUX = POL == 0 ? 17 : (POL == 1 ? 2 : (POL == 3 ? XAMD_LEAN_LD_AUX : 0));
   constexpr int ST_AUX = POL == 3 ? XAMD_LEAN_ST_AUX : 2;
   __shared__ __attribute__((aligned(16))) float lds_all[4][2048];
@@ -117,6 +118,57 @@ __global__ __launch_bounds__(256) void gemm_f32_stream_kernel_lean(const char* p
   }
 }
 
+template <bool TA, bool TB, bool SINGLE, int POL, typename S>
+__global__ __launch_bounds__(256) void gemm_f32_stream_kernel_lean(const char* pa, const char* pb, char* pc, S bs_a, S bs_b, S bs_c, unsigned int nbatch,
+                                                                   unsigned int lda, unsigned int ldb, unsigned int ldc,
+                                                                   unsigned int nchunks, unsigned int kchunks, long long brs_a, long long brs_b) {
+  lean_launch_body<TA, TB, SINGLE, POL, S>(pa, pb, pc, bs_a, bs_b, bs_c, nbatch, lda, ldb, ldc, nchunks, kchunks, brs_a, brs_b);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Several EQUAL launches in one grid (capture-time fusion): launches that differ in their three bases only, folded into one graph node
+// while the graph is built.  Grid (ceil(nbatch / 4), G): blockIdx.y selects the launch, everything else is the kernel above -- the same function, so the
+// results are bit for bit those of G separate launches; what goes is G - 1 dependent kernel boundaries and G - 1 fills and drains of the chip.
+// Arguments: the scalars first, so that the dispatch still preloads them (the three 32-bit batch strides, nbatch, lda, ldb, ldc, the chunk fields: 14
+// dwords); the table of bases travels by value behind them and one entry is read with uniform scalar loads indexed by blockIdx.y (no scratch).  32-bit strides and
+// 16-byte aligned C (POL 0 and 3) only: everything else stays unfused.
+// ------------------------------------------------------------------------------------------------
+struct LeanMultiTable { FuseEntry e[kFuseCap]; };
+static_assert(sizeof(FuseEntry) == 32, "table entries are 32 bytes apart");
+template <bool TA, bool TB, bool SINGLE, int POL>
+__global__ __launch_bounds__(256) void gemm_f32_lean_multi_kernel(unsigned int bs_a, unsigned int bs_b, unsigned int bs_c, unsigned int nbatch,
+                                                                  unsigned int lda, unsigned int ldb, unsigned int ldc, unsigned int nchunks, unsigned int kchunks,
+                                                                  long long brs_a, long long brs_b, const LeanMultiTable table) {
+  const FuseEntry e = table.e[blockIdx.y];
+  lean_launch_body<TA, TB, SINGLE, POL, unsigned int>((const char*)e.a, (const char*)e.b, (char*)e.c, bs_a, bs_b, bs_c, nbatch, lda, ldb, ldc, nchunks, kchunks, brs_a, brs_b);
+}
+
+template <bool TA, bool TB, bool SINGLE> static const void* lean_multi_pol(int pol) {
+  return pol == 0 ? (const void*)gemm_f32_lean_multi_kernel<TA, TB, SINGLE, 0> : (const void*)gemm_f32_lean_multi_kernel<TA, TB, SINGLE, 3>;
+}
+template <bool TA, bool TB> static const void* lean_multi_single(bool single, int pol) { return single ? lean_multi_pol<TA, TB, true>(pol) : lean_multi_pol<TA, TB, false>(pol); }
+static const void* lean_multi_function(bool ta, bool tb, bool single, int pol) {
+  return !ta ? (!tb ? lean_multi_single<false, false>(single, pol) : lean_multi_single<false, true>(single, pol))
+             : (!tb ? lean_multi_single<true, false>(single, pol) : lean_multi_single<true, true>(single, pol));
+}
+
+// The capture state of `st` as the fusion needs it: true when the stream is being captured and everything issued to it so far ends in exactly ONE node.
+// (The dependency array belongs to the runtime and is valid until the next HIP call only: the one node is copied out here.)
+static bool lean_capture_tail(hipStream_t st, unsigned long long* id, hipGraphNode_t* node, bool* capturing) {
+  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+  const hipGraphNode_t* deps = nullptr;
+  size_t ndeps = 0;
+  hipGraph_t graph = nullptr;
+  *capturing = false;
+  const hipError_t e = hipStreamGetCaptureInfo_v2(st, &status, id, &graph, &deps, &ndeps);
+  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (status != hipStreamCaptureStatusActive) return false;
+  *capturing = true;
+  if (ndeps != 1 || deps == nullptr) return false;
+  *node = deps[0];
+  return true;
+}
+
 // pol: 0..3 as above (chosen by launch_gemm); the operands are 16-byte aligned exact 32 x 32 tiles (f32_lean_ok)
 int launch_gemm_f32_lean(const GemmArgs& a, int pol, void* stream) {
   hipStream_t st = (hipStream_t)stream;
@@ -127,6 +179,49 @@ int launch_gemm_f32_lean(const GemmArgs& a, int pol, void* stream) {
   const unsigned int nbatch = (unsigned int)a.nbatch, lda = (unsigned int)a.lda, ldb = (unsigned int)a.ldb, ldc = (unsigned int)a.ldc;
   auto fits32 = [](long long s) { return s >= 0 && s < (1ll << 32); };
   const bool narrow = fits32(a.bs_a) && fits32(a.bs_b) && fits32(a.bs_c);
+  // ---- capture-time fusion: on a stream that is being captured, a launch that equals the one before it apart from its bases and is address-independent of
+  // every launch in that one's graph node joins the node instead of becoming a node of its own (rules: DESIGN.md section 5c, include/libxsmm_hip.h)
+  FuseState& f = tls().fuse;
+  const int limit = f.handle ? capture_fusion_limit() : 0;
+  // never asked of the NULL stream: it cannot be captured, and the query would invalidate another stream's global-mode capture
+  bool candidate = limit >= 2 && st != nullptr && narrow && (pol == 0 || pol == 3) && tls().pipe_lanes <= 1 && brs_a >= 0 && brs_b >= 0;
+  FuseKey key; FuseEntry entry{a.a, a.b, a.c, 0ull}; FuseLaunch range;
+  unsigned long long capture_id = 0;
+  if (candidate) {
+    size_t ea = 0, eb = 0, ec = 0;
+    key.handle = f.handle; key.bs_a = (unsigned int)a.bs_a; key.bs_b = (unsigned int)a.bs_b; key.bs_c = (unsigned int)a.bs_c; key.nbatch = nbatch;
+    key.lda = lda; key.ldb = ldb; key.ldc = ldc; key.nchunks = nchunks; key.kchunks = kchunks; key.brs_a = brs_a; key.brs_b = brs_b; key.pol = pol; key.ta = ta; key.tb = tb;
+    candidate = fuse_extent(a.br_count, brs_a, lda, (unsigned long long)(ta ? a.m : a.k), 4, &ea) && fuse_extent(a.br_count, brs_b, ldb, (unsigned long long)(tb ? a.k : a.n), 4, &eb) &&
+                fuse_extent(1, 0, ldc, (unsigned long long)a.n, 4, &ec) && fuse_range((uintptr_t)a.a, nbatch, a.bs_a, ea, &range.a) &&
+                fuse_range((uintptr_t)a.b, nbatch, a.bs_b, eb, &range.b) && fuse_range((uintptr_t)a.c, nbatch, a.bs_c, ec, &range.c);
+  }
+  if (candidate) {
+    hipGraphNode_t tail = nullptr;
+    bool capturing = false;
+    const bool one_tail = lean_capture_tail(st, &capture_id, &tail, &capturing);
+    if (!capturing) { candidate = false; f.n = 0; }
+    else if (one_tail && f.n > 0 && f.n < limit && f.n < kFuseCap && f.capture_id == capture_id && f.stream == (void*)st && f.node == (void*)tail && f.key == key &&
+             fuse_independent(range, f.range, f.n)) {
+      LeanMultiTable table{};
+      for (int i = 0; i < f.n; ++i) table.e[i] = f.entry[i];
+      table.e[f.n] = entry;
+      unsigned int bs[3] = {key.bs_a, key.bs_b, key.bs_c}, nb = nbatch, ld[3] = {lda, ldb, ldc}, nch = nchunks, kch = kchunks;
+      long long brs[2] = {brs_a, brs_b};
+      void* params[12] = {&bs[0], &bs[1], &bs[2], &nb, &ld[0], &ld[1], &ld[2], &nch, &kch, &brs[0], &brs[1], &table};
+      hipKernelNodeParams np{};
+      np.func = const_cast<void*>(lean_multi_function(ta, tb, nchunks == 1, pol));
+      np.gridDim = dim3(grid.x, (unsigned int)(f.n + 1), 1); np.blockDim = dim3(256, 1, 1);
+      np.sharedMemBytes = 0; np.kernelParams = params; np.extra = nullptr;
+      const hipError_t e = hipGraphKernelNodeSetParams(tail, &np);
+      if (e == hipSuccess) {
+        f.entry[f.n] = entry; f.range[f.n] = range; ++f.n; ++f.folded;
+        return 0;
+      }
+      (void)hipGetLastError();
+      f.n = 0; candidate = false;
+      capture_fusion_disable(hipGetErrorString(e));          // no other way is tried: the launch leaves on its own below
+    }
+  }
 #define LEAN_ARGS_(S_) (const char*)a.a, (const char*)a.b, (char*)a.c, (S_)a.bs_a, (S_)a.bs_b, (S_)a.bs_c, nbatch, lda, ldb, ldc, nchunks, kchunks, brs_a, brs_b
 #define LAUNCH_LEAN__(TA_, TB_, S_, P_) do { if (narrow) hipLaunchKernelGGL((gemm_f32_stream_kernel_lean<TA_, TB_, S_, P_, unsigned int>), grid, dim3(256), 0, st, LEAN_ARGS_(unsigned int)); \
                                              else hipLaunchKernelGGL((gemm_f32_stream_kernel_lean<TA_, TB_, S_, P_, long long>), grid, dim3(256), 0, st, LEAN_ARGS_(long long)); } while (0)
@@ -137,7 +232,17 @@ int launch_gemm_f32_lean(const GemmArgs& a, int pol, void* stream) {
 #undef LAUNCH_LEAN_S_
 #undef LAUNCH_LEAN__
 #undef LEAN_ARGS_
-  return (int)hipGetLastError();
+  const int err = (int)hipGetLastError();
+  if (candidate) {          // captured as a node of its own: the node the next equal, independent launch may join
+    hipGraphNode_t tail = nullptr;
+    bool capturing = false;
+    unsigned long long id_now = 0;
+    f.n = 0;
+    if (err == 0 && lean_capture_tail(st, &id_now, &tail, &capturing) && id_now == capture_id) {
+      f.n = 1; f.capture_id = capture_id; f.stream = (void*)st; f.node = (void*)tail; f.key = key; f.entry[0] = entry; f.range[0] = range;
+    }
+  }
+  return err;
 }
 
 }  // namespace xamd

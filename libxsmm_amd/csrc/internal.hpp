@@ -18,6 +18,7 @@
 #include <atomic>
 #include <string>
 #include <vector>
+#include "capture_fuse.hpp"
 
 // ---- opaque descriptors (users only ever hold pointers into a libxsmm_descriptor_blob) ----
 // Own layout; only the *behaviour* of the reference's init functions is reproduced
@@ -275,7 +276,11 @@ struct ThreadState {
   void* pipe_user = nullptr;             // the caller's stream while a pipeline section is open
   void* pipe_stream[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   void* pipe_event[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [8]: the fork point
+  FuseState fuse;             // capture-time fusion of lean launches (capture_fuse.hpp, gemm_lean_kernels.hip)
 };
+// libxsmm_hip_set_capture_fusion / LIBXSMM_HIP_CAPTURE_FUSION: launches one graph node may hold (0: off), process-wide
+int capture_fusion_limit();
+void capture_fusion_disable(const char* why);       // a graph call failed: off for the process, the reason goes to the thread's error state
 ThreadState& tls();
 void set_error(int code, const char* fmt, ...);
 

@@ -59,6 +59,7 @@ int g_device_count = -1;
 bool g_warned_nodevice = false;
 bool g_dryrun = false;                // LIBXSMM_HIP_DRYRUN=1: dispatch works without a device (registry tests); calling a kernel is an error
 std::atomic<unsigned int> g_generation{1};   // bumped by libxsmm_finalize: invalidates every thread's dispatch cache
+std::atomic<int> g_capture_fusion{-1};       // launches one captured graph node may hold (0: off; -1: LIBXSMM_HIP_CAPTURE_FUSION not read yet)
 
 unsigned char* g_thunk_pool = nullptr;       // kSlots * kThunkBytes, nullptr: static trampolines only
 std::vector<bool> g_thunk_page_ready;
@@ -771,7 +772,10 @@ void run_gemm(KernelCtx* k, const void* param, const BatchSpec& b) {
       return;
     }
   }
+  // a plain strided batch that is being captured may be folded into the graph node of the launch before it (the lean launcher decides: DESIGN.md section 5c)
+  tls().fuse.handle = (b.count > 1 && !b.la && !b.inner && t_nest == 0) ? (const void*)k : nullptr;
   const int err = launch_gemm(a, tls().stream, &kname);
+  tls().fuse.handle = nullptr;
   if (kname) { if (b.count > 1 || b.la) k->kname_batched = kname; else k->kname_single = kname; }   // what actually ran
   finish_launch(err, kname);
 }
@@ -1246,7 +1250,7 @@ void coalesce_flush() {
   la.clear(); lb.clear(); lc.clear();
   q.a.swap(la); q.b.swap(lb); q.c.swap(lc);             // keep the capacity
 }
-static bool ranges_overlap(uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return a0 < b0 + bn && b0 < a0 + an; }
+// (ranges_overlap: capture_fuse.hpp)
 // true: the call has been queued
 bool coalesce_try(KernelCtx* k, const void* param) {
   if (k->kind != K_GEMM || t_nest > 0 || tls().pipe_lanes > 1 || !param) return false;
@@ -1367,6 +1371,22 @@ void rt_note(const char* what, int a, int b, int c) { vlog(1, "%s (%d, %d, %d)",
 void* rt_stream() { return tls().stream; }
 int rt_jit_mode() { return jit_mode(); }
 bool rt_dryrun() { return g_dryrun; }
+
+// capture-time fusion: -1 = not read from the environment yet
+int capture_fusion_limit() {
+  int v = g_capture_fusion.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = std::getenv("LIBXSMM_HIP_CAPTURE_FUSION");
+    const int want = e ? std::atoi(e) : kFuseCap;
+    const int init = want < 2 ? 0 : std::min(want, kFuseCap);
+    if (g_capture_fusion.compare_exchange_strong(v, init, std::memory_order_relaxed)) v = init;
+  }
+  return v;
+}
+void capture_fusion_disable(const char* why) {
+  g_capture_fusion.store(0, std::memory_order_relaxed);
+  set_error(-5, "capture fusion switched off for this process: %s (the launch was issued on its own)", why);
+}
 
 void invoke(int slot, const void* param) {
   KernelCtx* k = g_slots[slot];
@@ -2134,6 +2154,12 @@ LIBXSMM_API int libxsmm_hip_probe_mfma(libxsmm_datatype datatype, const void* op
   if (err != 0) { set_error(err, "launch of mfma_probe_kernel failed: %s", hipGetErrorString((hipError_t)err)); return EXIT_FAILURE; }
   return EXIT_SUCCESS;
 }
+LIBXSMM_API int libxsmm_hip_set_capture_fusion(int max_launches) {
+  const int before = xamd::capture_fusion_limit();
+  g_capture_fusion.store(max_launches < 2 ? 0 : std::min(max_launches, xamd::kFuseCap), std::memory_order_relaxed);
+  return before;
+}
+LIBXSMM_API unsigned long long libxsmm_hip_fused_launch_count(int reset) { const unsigned long long n = tls().fuse.folded; if (reset) tls().fuse.folded = 0; return n; }
 LIBXSMM_API unsigned long long libxsmm_hip_launch_count(int reset) { const unsigned long long n = tls().launches; if (reset) tls().launches = 0; return n; }
 LIBXSMM_API const char* libxsmm_hip_kernel_name(const void* kernel, int batched) {
   KernelCtx* c = ctx_from_handle(kernel);
