@@ -905,6 +905,28 @@ __global__ __launch_bounds__(256) void gs_rows_lds_kernel(MeltwArgs p, int rows)
 
 // reductions over rows (collapse i: one wave per column, shuffle tree) or columns (collapse j:
 // one thread per row, serial over j -- reads stay coalesced along i) [ref: :1065-1441]
+// Start values of MAX / MIN / ABSMAX, per direction, as the reference has them:
+//   over rows     the reference starts at the column's first element [ref: :1362]; here every accumulator (idle lanes and out-of-range columns included)
+//                 starts at -infinity / +infinity / 0, which gives the same value for every input without NaN and costs no load;
+//   over columns  -FLT_MAX / FLT_MAX / 0 [ref: :1378,:1405]: a row of -inf has the MAX -FLT_MAX there, and here.
+// Contract for MAX / MIN / ABSMAX: inputs without NaN.  Lanes, slices and chunks are folded as trees, and no tree can reproduce the reference's
+// order-dependent result on a NaN; over rows the result equals the serial loop in value (a lane tree may keep the other zero of a +0 / -0 tie).
+// A bf16 operand or start value is loaded as the reference loads it: a denormal is a signed zero (mw_load_ew / mw_bf2f_daz).
+// One step over columns in the reference's operand order -- MAX(x, acc), MIN(x, acc), MAX(ABS(x), acc) with MAX(A, B) = A < B ? B : A, MIN(A, B) = A < B ? A : B,
+// ABS(A) = 0 <= A ? A : -A (a -0 stays -0) -- so the serial forms (the general kernel, one column slice, the listed columns) equal the reference bit for bit, the
+// zero a +0 / -0 tie keeps included.  Partial results of slices and chunks are folded with the same step (ABS leaves them as they are); for MAX / MIN / ABSMAX slices and chunks
+// are contiguous column ranges folded in column order, so the sixteen-slice and the two-pass form equal the serial loop bit for bit as well.
+__device__ __forceinline__ float red_abs(float a) { return (0.0f <= a) ? a : -a; }
+__device__ __forceinline__ float red_col_step(int type, float acc, float x) {
+  if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) return (x < acc) ? acc : x;
+  if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) return (x < acc) ? x : acc;
+  const float ax = red_abs(x);
+  return (ax < acc) ? acc : ax;
+}
+__device__ __forceinline__ float red_ident(int type, bool rows) {
+  const float top = rows ? __builtin_inff() : 3.402823466e+38f;
+  return (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) ? -top : (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) ? top : 0.0f;
+}
 __global__ __launch_bounds__(256) void reduce_kernel(MeltwArgs p) {
   const bool rows = (p.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS) != 0;
   const bool init_acc = (p.flags & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_INIT_ACC) != 0;
@@ -916,9 +938,10 @@ __global__ __launch_bounds__(256) void reduce_kernel(MeltwArgs p) {
   gptr out = (gptr)p.out + (long long)blockIdx.y * p.bs_out;
   const long long result_size = rows ? p.n : p.ldo;
   gptr out2 = (want_x && want_x2) ? out + result_size * mw_size(p.out_type) : out;
-  const float ident = (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) ? -3.402823466e+38f : (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) ? 3.402823466e+38f : 0.0f;
+  const float ident = red_ident(type, rows);
   auto combine = [&](float a, float x) {
     if (is_add) return a + x;
+    if (!rows) return red_col_step(type, a, x);
     if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) return (a < x) ? x : a;
     if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) return (a > x) ? x : a;
     return fmaxf(fabsf(a), fabsf(x));
@@ -929,12 +952,12 @@ __global__ __launch_bounds__(256) void reduce_kernel(MeltwArgs p) {
     if (j >= p.n) return;
     float sx = ident, sx2 = 0.0f;
     for (int i = lane; i < p.m; i += 64) {
-      const float x = mw_load(in, i + (long long)j * p.ldi, p.in0_type);
+      const float x = mw_load_ew(in, i + (long long)j * p.ldi, p.in0_type);
       sx = combine(sx, x); sx2 += x * x;
     }
     for (int off = 32; off > 0; off >>= 1) { sx = combine(sx, __shfl_xor(sx, off)); sx2 += __shfl_xor(sx2, off); }
     if (lane == 0) {
-      if (is_add && init_acc) { if (want_x) sx += mw_load(out, j, p.out_type); if (want_x2) sx2 += mw_load(out2, j, p.out_type); }
+      if (is_add && init_acc) { if (want_x) sx += mw_load_ew(out, j, p.out_type); if (want_x2) sx2 += mw_load_ew(out2, j, p.out_type); }
       if (want_x) mw_store(out, j, p.out_type, sx);
       if (want_x2) mw_store(out2, j, p.out_type, sx2);
     }
@@ -943,10 +966,10 @@ __global__ __launch_bounds__(256) void reduce_kernel(MeltwArgs p) {
     if (i >= p.m) return;
     float sx = ident, sx2 = 0.0f;
     for (int j = 0; j < p.n; ++j) {
-      const float x = mw_load(in, i + (long long)j * p.ldi, p.in0_type);
+      const float x = mw_load_ew(in, i + (long long)j * p.ldi, p.in0_type);
       sx = combine(sx, x); sx2 += x * x;
     }
-    if (is_add && init_acc) { if (want_x) sx += mw_load(out, i, p.out_type); if (want_x2) sx2 += mw_load(out2, i, p.out_type); }
+    if (is_add && init_acc) { if (want_x) sx += mw_load_ew(out, i, p.out_type); if (want_x2) sx2 += mw_load_ew(out2, i, p.out_type); }
     if (want_x) mw_store(out, i, p.out_type, sx);
     if (want_x2) mw_store(out2, i, p.out_type, sx2);
   }
@@ -956,11 +979,11 @@ __global__ __launch_bounds__(256) void reduce_kernel(MeltwArgs p) {
 //   REDUCE_ROWS (one result per column): a group of G = min(64, pow2(m/4)) lanes owns a column, every lane adds 4-element
 //     vectors with stride G, the group is folded with xor-shuffles; a wave covers 64/G columns (small m keeps all lanes busy).
 //   REDUCE_COLS (one result per 4 rows): a thread owns 4 consecutive rows and, when n >= 256, one of 16 column slices
-//     (columns slice, slice+16, ...); the 16 partial vectors are combined in slice order through LDS.  For n < 256 there is
+//     (MAX / MIN / ABSMAX: contiguous column ranges; sums: columns slice, slice+16, ...); the 16 partial vectors are combined in slice order through LDS.  For n < 256 there is
 //     one slice and the sum runs in column order, bit-identical to the general kernel and the oracle.
 template <bool BF16IN>
 __device__ __forceinline__ void red_load4(float (&x)[4], gcptr in, long long idx) {
-  if (BF16IN) { const u16x4 v = *(GM const u16x4*)((GM const unsigned short*)in + idx); for (int e = 0; e < 4; ++e) x[e] = mw_bf2f(v[e]); }
+  if (BF16IN) { const u16x4 v = *(GM const u16x4*)((GM const unsigned short*)in + idx); for (int e = 0; e < 4; ++e) x[e] = mw_bf2f_daz(v[e]); }
   else { const f32x4 v = *(GM const f32x4*)((GM const float*)in + idx); for (int e = 0; e < 4; ++e) x[e] = v[e]; }
 }
 // RGL: row groups per block of the REDUCE_COLS form (16: 16 column slices per block, tiles; 64: 4 slices, whole 1 KiB row segments per wave -- the
@@ -979,9 +1002,10 @@ __global__ __launch_bounds__(256) void reduce_vec_kernel(MeltwArgs p, int G, int
   gptr out = (gptr)p.out + (long long)blockIdx.y * p.bs_out;
   const long long result_size = rows ? p.n : p.ldo;
   gptr out2 = (want_x && want_x2) ? out + result_size * mw_size(p.out_type) : out;
-  const float ident = (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) ? -3.402823466e+38f : (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) ? 3.402823466e+38f : 0.0f;
+  const float ident = red_ident(type, rows);
   auto combine = [&](float a, float x) {
     if (is_add) return a + x;
+    if (!rows) return red_col_step(type, a, x);
     if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) return (a < x) ? x : a;
     if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) return (a > x) ? x : a;
     return fmaxf(fabsf(a), fabsf(x));
@@ -1008,7 +1032,7 @@ __global__ __launch_bounds__(256) void reduce_vec_kernel(MeltwArgs p, int G, int
         for (int off = G >> 1; off > 0; off >>= 1) { sx = combine(sx, __shfl_xor(sx, off)); sx2 += __shfl_xor(sx2, off); }
         const int j = j0 + u;
         if (l == 0 && j < p.n) {
-          if (is_add && init_acc) { if (want_x) sx += mw_load(out, j, p.out_type); if (want_x2) sx2 += mw_load(out2, j, p.out_type); }
+          if (is_add && init_acc) { if (want_x) sx += mw_load_ew(out, j, p.out_type); if (want_x2) sx2 += mw_load_ew(out2, j, p.out_type); }
           if (want_x) mw_store(out, j, p.out_type, sx);
           if (want_x2) mw_store(out2, j, p.out_type, sx2);
         }
@@ -1046,7 +1070,7 @@ __global__ __launch_bounds__(256) void reduce_vec_kernel(MeltwArgs p, int G, int
     }
     for (int off = G >> 1; off > 0; off >>= 1) { sx = combine(sx, __shfl_xor(sx, off)); sx2 += __shfl_xor(sx2, off); }
     if (l == 0 && j < p.n) {
-      if (is_add && init_acc) { if (want_x) sx += mw_load(out, j, p.out_type); if (want_x2) sx2 += mw_load(out2, j, p.out_type); }
+      if (is_add && init_acc) { if (want_x) sx += mw_load_ew(out, j, p.out_type); if (want_x2) sx2 += mw_load_ew(out2, j, p.out_type); }
       if (want_x) mw_store(out, j, p.out_type, sx);
       if (want_x2) mw_store(out2, j, p.out_type, sx2);
     }
@@ -1056,29 +1080,36 @@ __global__ __launch_bounds__(256) void reduce_vec_kernel(MeltwArgs p, int G, int
     float sx[4] = {ident, ident, ident, ident}, sx2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     // two-pass form (partial != NULL): blockIdx.z owns columns [z*chunk, (z+1)*chunk) and writes raw partial sums
     const int jbeg = partial ? (int)blockIdx.z * chunk : 0, jend = partial ? ((jbeg + chunk < p.n) ? jbeg + chunk : p.n) : p.n;
-    if (rg < m4 && sl < slices) {
-      int j = jbeg + sl;
+    // MAX / MIN / ABSMAX: slice sl owns the CONTIGUOUS columns [jbeg + sl * len, jbeg + (sl + 1) * len) and the slices are folded in slice order, so the columns are
+    // walked in the reference's order (ties included); a slice without a column (a short last chunk) is left out of the fold -- its start value +0 would replace an
+    // ABSMAX of -0.  Sums keep the INTERLEAVED walk (slice sl: columns sl, sl + slices, ...: a wave's request is four adjacent columns): no order to keep there, and
+    // on 512 tiles of 64 x 1024 f32 the contiguous walk measured 34.3 against 28.2 us (MAX pays it: 35.5 -> 47.6; one 4096 x 8192 matrix: 33.9 either way; 128 tiles of 256 x 512: 17.4 against 19.2).
+    const bool contig = !is_add;
+    const int len = (jend - jbeg + slices - 1) / slices, nsl = contig ? (jend - jbeg + len - 1) / len : slices, st = contig ? 1 : slices;
+    if (rg < m4 && sl < nsl) {
+      int j = jbeg + (contig ? sl * len : sl);
+      const int je = (contig && j + len < jend) ? j + len : jend;
       // sixteen columns in flight per thread first (a wave then has 16 KiB on its way: with four, 2048 waves of the two-pass form kept 8 MB in flight and ran at
       // 4.2 TB/s -- the round trip, not the memory system), folded in column order like the loops below: the same sums
-      for (; j + 15 * slices < jend; j += 16 * slices) {
+      for (; j + 15 * st < je; j += 16 * st) {
         float x[16][4];
 #pragma unroll
-        for (int u = 0; u < 16; ++u) red_load4<BF16IN>(x[u], in, 4ll * rg + (long long)(j + u * slices) * p.ldi);
+        for (int u = 0; u < 16; ++u) red_load4<BF16IN>(x[u], in, 4ll * rg + (long long)(j + u * st) * p.ldi);
 #pragma unroll
         for (int u = 0; u < 16; ++u)
 #pragma unroll
           for (int e = 0; e < 4; ++e) { sx[e] = combine(sx[e], x[u][e]); sx2[e] += x[u][e] * x[u][e]; }
       }
-      for (; j + 3 * slices < jend; j += 4 * slices) {       // four columns in flight, folded in column order
+      for (; j + 3 * st < je; j += 4 * st) {       // four columns in flight, folded in column order
         float x[4][4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) red_load4<BF16IN>(x[u], in, 4ll * rg + (long long)(j + u * slices) * p.ldi);
+        for (int u = 0; u < 4; ++u) red_load4<BF16IN>(x[u], in, 4ll * rg + (long long)(j + u * st) * p.ldi);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
           for (int e = 0; e < 4; ++e) { sx[e] = combine(sx[e], x[u][e]); sx2[e] += x[u][e] * x[u][e]; }
       }
-      for (; j < jend; j += slices) {
+      for (; j < je; j += st) {
         float x[4]; red_load4<BF16IN>(x, in, 4ll * rg + (long long)j * p.ldi);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { sx[e] = combine(sx[e], x[e]); sx2[e] += x[e] * x[e]; }
@@ -1089,7 +1120,7 @@ __global__ __launch_bounds__(256) void reduce_vec_kernel(MeltwArgs p, int G, int
       for (int e = 0; e < 4; ++e) { part[0][sl][rg_l][e] = sx[e]; part[1][sl][rg_l][e] = sx2[e]; }
       __syncthreads();
       if (sl != 0) return;
-      for (int s2 = 1; s2 < slices; ++s2)
+      for (int s2 = 1; s2 < nsl; ++s2)
 #pragma unroll
         for (int e = 0; e < 4; ++e) { sx[e] = combine(sx[e], part[0][s2][rg_l][e]); sx2[e] += part[1][s2][rg_l][e]; }
     } else if (sl != 0) return;
@@ -1104,7 +1135,7 @@ __global__ __launch_bounds__(256) void reduce_vec_kernel(MeltwArgs p, int G, int
     for (int e = 0; e < 4; ++e) {
       const long long i = 4ll * rg + e;
       float a = sx[e], b = sx2[e];
-      if (is_add && init_acc) { if (want_x) a += mw_load(out, i, p.out_type); if (want_x2) b += mw_load(out2, i, p.out_type); }
+      if (is_add && init_acc) { if (want_x) a += mw_load_ew(out, i, p.out_type); if (want_x2) b += mw_load_ew(out2, i, p.out_type); }
       if (want_x) mw_store(out, i, p.out_type, a);
       if (want_x2) mw_store(out2, i, p.out_type, b);
     }
@@ -1136,9 +1167,9 @@ __global__ __launch_bounds__(256) void reduce_cols_listed_kernel(MeltwArgs p) {
   unsigned long long arg = 0; bool found = false;
   for (unsigned long long jj = 0; jj < n_cols; ++jj) {
     const unsigned long long j = listed ? (idx4 ? (unsigned long long)idx32[jj] : idx64[jj]) : jj;     // wave-uniform: one scalar load
-    float x = mw_load(in, (long long)i + (long long)j * p.ldi, p.in0_type);
+    float x = mw_load_ew(in, (long long)i + (long long)j * p.ldi, p.in0_type);
     if (op == 0) { acc += x; continue; }
-    if (op == 3) x = fabsf(x);
+    if (op == 3) x = red_abs(x);
     if (op == 1 || op == 3) {
       if (record) { if (x >= acc) { acc = x; arg = j; found = true; } }
       else acc = (x < acc) ? acc : x;
@@ -1369,7 +1400,7 @@ __global__ __launch_bounds__(256) void reduce_combine_kernel(MeltwArgs p, const 
   GM const float* px = (GM const float*)partial + i;
   float a = px[0], b = want_x2 ? px[p.m] : 0.0f;
   auto fold = [&](float x, float x2) {
-    if (is_add) a += x; else if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) a = (a < x) ? x : a; else if (type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) a = (a > x) ? x : a; else a = fmaxf(fabsf(a), fabsf(x));
+    if (is_add) a += x; else a = red_col_step(type, a, x);
     b += x2;
   };
   // sixteen chunks' partial sums in flight per thread, folded in chunk order (the loop used to ask for one pair at a time: with 128 chunks the 16 workgroups of this
@@ -1385,7 +1416,7 @@ __global__ __launch_bounds__(256) void reduce_combine_kernel(MeltwArgs p, const 
   for (; z < nchunks; ++z) fold(px[(long long)z * 2 * p.m], want_x2 ? px[((long long)z * 2 + 1) * p.m] : 0.0f);
   gptr out = (gptr)p.out;
   gptr out2 = (want_x && want_x2) ? out + (long long)p.ldo * mw_size(p.out_type) : out;
-  if (is_add && init_acc) { if (want_x) a += mw_load(out, i, p.out_type); if (want_x2) b += mw_load(out2, i, p.out_type); }
+  if (is_add && init_acc) { if (want_x) a += mw_load_ew(out, i, p.out_type); if (want_x2) b += mw_load_ew(out2, i, p.out_type); }
   if (want_x) mw_store(out, i, p.out_type, a);
   if (want_x2) mw_store(out2, i, p.out_type, b);
 }

@@ -270,7 +270,11 @@ int bcast_of(const EqnNode& parent, int operand) {   // 0 none, 1 row, 2 col, 3 
 
 // A reduction (one node, or a REDUCE_COLS / REDUCE_ROWS pair) that folds an element-wise M x N operand into ONE number: the max and the sum
 // of a softmax, the sum of a softmax backward pass [ref: samples/equation/equation_softmax.c:527-538,676-688]
-struct ScalarReduce { int src; int fold; bool square; };     // fold: 0 add, 1 max, 2 min
+// `clamped`: the start value of a MAX / MIN.  The step chain runs the reference's TPPs: a REDUCE_COLS node starts at -FLT_MAX / FLT_MAX, a REDUCE_ROWS node at its
+// operand's first element [ref: mateltwise ref :1362,:1378,:1405].  So a nesting with a REDUCE_COLS node in it (rows of cols: the softmax's) never yields less than
+// -FLT_MAX, and one made of REDUCE_ROWS nodes only yields the true extremum, -inf included: there the fold starts at -inf / +inf (equal to "the first element" for
+// inputs without NaN).
+struct ScalarReduce { int src; int fold; bool square; bool clamped; };     // fold: 0 add, 1 max, 2 min
 bool scalar_reduce(const Equation& e, int id, int M, int N, ScalarReduce& r) {
   const EqnNode& nd = e.nodes[id];
   const auto kind = [](int op, int& fold, bool& sq) {
@@ -284,12 +288,13 @@ bool scalar_reduce(const Equation& e, int id, int M, int N, ScalarReduce& r) {
   };
   const unsigned int dirs = LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS | LIBXSMM_MELTW_FLAG_UNARY_REDUCE_COLS;
   if (nd.kind != EQ_UNARY || nd.m != 1 || nd.n != 1 || nd.dtype != LIBXSMM_DATATYPE_F32 || !kind(nd.op, r.fold, r.square) || (nd.flags & ~dirs) || !(nd.flags & dirs)) return false;
-  r.src = nd.child[0];
+  const auto over_cols = [](unsigned int f) { return !(f & LIBXSMM_MELTW_FLAG_UNARY_REDUCE_ROWS); };      // REDUCE_ROWS decides where both are set (the shape rule above)
+  r.src = nd.child[0]; r.clamped = over_cols(nd.flags);
   const EqnNode& c = e.nodes[nd.child[0]];
   if (c.kind == EQ_UNARY && is_reduce(c.op)) {
     int f2 = 0; bool s2 = false;
     if (c.dtype != LIBXSMM_DATATYPE_F32 || !kind(c.op, f2, s2) || f2 != r.fold || r.square || (c.flags & ~dirs) || !(c.flags & dirs)) return false;
-    r.square = s2; r.src = c.child[0];
+    r.square = s2; r.src = c.child[0]; r.clamped = r.clamped || over_cols(c.flags);
   }
   return e.nodes[r.src].m == M && e.nodes[r.src].n == N;
 }
@@ -498,7 +503,7 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
       return true;
     }
     if (nd.dtype != LIBXSMM_DATATYPE_F32) return false;
-    ScalarReduce r; r.src = -1; r.fold = 0; r.square = false;
+    ScalarReduce r; r.src = -1; r.fold = 0; r.square = false; r.clamped = true;
     const bool dot = nd.kind == EQ_BINARY && nd.op == LIBXSMM_MELTW_TYPE_BINARY_MUL_AND_REDUCE_TO_SCALAR_OP_ADD && nd.flags == 0;
     if (dot || scalar_reduce(e, id, M, N, r)) {
       std::string body, x, y, fold;
@@ -510,7 +515,8 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
         fold = r.fold == 1 ? "acc = (acc < " + x + "[e]) ? " + x + "[e] : acc;" : r.fold == 2 ? "acc = (acc > " + x + "[e]) ? " + x + "[e] : acc;"
              : r.square ? "{ const float sq = " + x + "[e] * " + x + "[e]; acc = acc + sq; }" : "acc = acc + " + x + "[e];";
       }
-      const char* init = r.fold == 1 ? "-3.402823466e+38f" : r.fold == 2 ? "3.402823466e+38f" : "0.0f";      // [ref: mateltwise ref :1386,:1415]
+      const char* init = r.fold == 0 ? "0.0f" : r.clamped ? (r.fold == 1 ? "-3.402823466e+38f" : "3.402823466e+38f")      // [ref: mateltwise ref :1378,:1405]
+                                                  : (r.fold == 1 ? "-__builtin_inff()" : "__builtin_inff()");            // [ref: mateltwise ref :1362]
       const char* combine = r.fold == 1 ? "(acc < o) ? o : acc" : r.fold == 2 ? "(acc > o) ? o : acc" : "acc + o";
       phases += "  float " + name + ";\n  { float acc = " + init + ";\n" + unit_loop + body + "  _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) " + fold + "\n  }\n"
                 "  part[threadIdx.x] = acc; __syncthreads();\n"
@@ -559,7 +565,8 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
     ++n_vec;
     lds_decl += "  __shared__ float " + name + "[" + std::to_string(M) + "];\n";
     const char* init = fold == 1 ? "-3.402823466e+38f" : fold == 2 ? "3.402823466e+38f" : "0.0f";
-    const std::string step = fold == 1 ? "acc[e] = (acc[e] < " + x + "[e]) ? " + x + "[e] : acc[e];" : fold == 2 ? "acc[e] = (acc[e] > " + x + "[e]) ? " + x + "[e] : acc[e];"
+    // the reference's operand order over columns: MAX(x, acc) = x < acc ? acc : x, MIN(x, acc) = x < acc ? x : acc
+    const std::string step = fold == 1 ? "acc[e] = (" + x + "[e] < acc[e]) ? acc[e] : " + x + "[e];" : fold == 2 ? "acc[e] = (" + x + "[e] < acc[e]) ? " + x + "[e] : acc[e];"
                            : sq ? "{ const float sq = " + x + "[e] * " + x + "[e]; acc[e] = acc[e] + sq; }" : "acc[e] = acc[e] + " + x + "[e];";
     phases += "  for (long long ib = threadIdx.x; ib < " + std::to_string(M / 8) + "LL; ib += 256) {\n  const long long i = ib * 8;\n  float acc[8]; _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) acc[e] = " + init + ";\n"
               "  for (long long j = 0; j < " + std::to_string(N) + "LL; ++j) {\n" + body + "  _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) " + step + "\n  }\n"

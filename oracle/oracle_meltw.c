@@ -275,6 +275,10 @@ static long long oracle_rng_width = 16;
 void oracle_set_rng_width(int w) { oracle_rng_width = (w >= 1 && w <= 16) ? w : 16; }
 
 /* ---- reductions  [:1065-1441], f32 compute ------------------------------------------------ */
+/* the reference's own comparison macros [ref: include/libxsmm_macros.h:635-637]: which operand a tie or a NaN keeps follows from their operand order */
+#define REF_ABS(A) (0 <= (A) ? (A) : -(A))
+#define REF_MIN(A, B) ((A) < (B) ? (A) : (B))
+#define REF_MAX(A, B) ((A) < (B) ? (B) : (A))
 static int is_reduce(int t) {
   switch (t) {
     case LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_ADD: case LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X2_OP_ADD:
@@ -307,7 +311,7 @@ static void reduce_cols_listed(const libxsmm_meltw_unary_param* p, const oracle_
       const unsigned long long j = listed ? (idx4 ? (unsigned long long)idx32[jj] : idx64[jj]) : jj;
       float x = get_f32(p->in.primary, i + (long long)j * ldi, d->in0_type);
       if (op == 0) { acc = acc + x; continue; }
-      if (op == 3) x = fabsf(x);
+      if (op == 3) x = REF_ABS(x);
       if (op == 1 || op == 3) {
         if (record) { if (x >= acc) { acc = x; if (idx4) arg32[i] = (unsigned int)j; else arg64[i] = j; } }
         else acc = (x < acc) ? acc : x;                                      /* LIBXSMM_MAX(in_val, acc) */
@@ -342,9 +346,15 @@ static void reduce(const libxsmm_meltw_unary_param* p, const oracle_meltw_desc* 
       const long long i = rows ? t : q, j = rows ? q : t;
       float x = get_f32(p->in.primary, i + j * ldi, d->in0_type);
       if (is_add) { sx = sx + x; sx2 = sx2 + x * x; }
-      else if (d->type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) sx = (sx < x) ? x : sx;
-      else if (d->type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) sx = (sx > x) ? x : sx;
-      else { const float ax = fabsf(x), as = fabsf(sx); sx = (as < ax) ? ax : as; }
+      else if (rows) {                 /* [:1365-1367] the accumulator is the FIRST operand: MAX(acc, x), MAX(ABS(acc), ABS(x)), MIN(acc, x) */
+        if (d->type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) sx = REF_MAX(sx, x);
+        else if (d->type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) sx = REF_MIN(sx, x);
+        else { const float as = REF_ABS(sx), ax = REF_ABS(x); sx = REF_MAX(as, ax); }
+      } else {                         /* [:1387,:1398,:1424] the accumulator is the SECOND operand: MAX(x, acc), MAX(ABS(x), acc), MIN(x, acc) */
+        if (d->type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MAX) sx = REF_MAX(x, sx);
+        else if (d->type == LIBXSMM_MELTW_TYPE_UNARY_REDUCE_X_OP_MIN) sx = REF_MIN(x, sx);
+        else { const float ax = REF_ABS(x); sx = REF_MAX(ax, sx); }
+      }
     }
     if (is_add && init_acc) {                                                                   /* [:1313-1324] */
       if (want_x) sx = sx + get_f32(out_x, q, d->out_type);

@@ -40,7 +40,7 @@ def build(api, tree, arg_shapes, comp=DT.F32):
     return idx
 
 
-REDUCES = (UNARY.REDUCE_X_OP_ADD, UNARY.REDUCE_X_OP_MAX, UNARY.REDUCE_X2_OP_ADD)
+REDUCES = (UNARY.REDUCE_X_OP_ADD, UNARY.REDUCE_X_OP_MAX, UNARY.REDUCE_X_OP_MIN, UNARY.REDUCE_X2_OP_ADD)
 
 
 def evaluate(tree, arg_shapes, arrays, out_shape, comp=DT.F32):
