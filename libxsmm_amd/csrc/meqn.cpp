@@ -204,19 +204,20 @@ void print_rpn(const Equation& e, int id) {
 // Conditions: every op is element-wise arithmetic with an f32 op type, every broadcast operand is an argument, all full
 // operands share the output's m x n, m and every leading dimension are multiples of 8.  One thread = 8 consecutive rows
 // of one column; the expression is emitted in post-order on 8-element register arrays with the SAME per-element
-// formulas as meltw_kernels.hip (contraction off), so the result is bit-identical to the step chain.
+// formulas as meltw_kernels.hip (contraction off) and the same loads (a bf16 denormal is a signed zero, mw_bf2f_daz), so the result is bit-identical to
+// the step chain (tests/test_meqn_parity_gpu.py holds every element-wise tree to that).
 const char* kFusedPrelude = R"SRC(
 #define GM __attribute__((address_space(1)))
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float daz(float x) { return ((__float_as_uint(x) & 0x7f800000u) == 0u) ? __uint_as_float(__float_as_uint(x) & 0x80000000u) : x; }
+__device__ __forceinline__ float daz(float x) { return (__builtin_fabsf(x) < 1.17549435e-38f) ? __uint_as_float(__float_as_uint(x) & 0x80000000u) : x; }      // (a compare with |x| as a source modifier: one operation fewer than testing the exponent field)
 __device__ __forceinline__ unsigned int f2bf_pk(float lo, float hi) { const f32x2 v = {daz(lo), daz(hi)}; return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2)); }
 __device__ __forceinline__ void ld_f32(float (&x)[8], GM const float* p) { const f32x4 a = *(GM const f32x4*)p, b = *(GM const f32x4*)(p + 4);
   x[0] = a[0]; x[1] = a[1]; x[2] = a[2]; x[3] = a[3]; x[4] = b[0]; x[5] = b[1]; x[6] = b[2]; x[7] = b[3]; }
 __device__ __forceinline__ void ld_bf16(float (&x)[8], GM const unsigned short* p) { const u32x4 v = *(GM const u32x4*)p;
-  _Pragma("unroll") for (int e = 0; e < 4; ++e) { x[2 * e] = __uint_as_float(v[e] << 16); x[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u); } }
+  _Pragma("unroll") for (int e = 0; e < 4; ++e) { x[2 * e] = daz(__uint_as_float(v[e] << 16)); x[2 * e + 1] = daz(__uint_as_float(v[e] & 0xffff0000u)); } }      // DAZ, as mw_bf2f_daz of the chain's TPP kernels
 __device__ __forceinline__ void st_f32(GM float* p, const float (&y)[8]) { f32x4 a, b; a[0] = y[0]; a[1] = y[1]; a[2] = y[2]; a[3] = y[3]; b[0] = y[4]; b[1] = y[5]; b[2] = y[6]; b[3] = y[7];
   *(GM f32x4*)p = a; *(GM f32x4*)(p + 4) = b; }
 __device__ __forceinline__ void st_bf16(GM unsigned short* p, const float (&y)[8]) { u32x4 v; _Pragma("unroll") for (int e = 0; e < 4; ++e) v[e] = f2bf_pk(y[2 * e], y[2 * e + 1]); *(GM u32x4*)p = v; }
@@ -326,7 +327,7 @@ void emit_accumulating(bool carry, const std::string& fname, long long units, in
   std::string step;                                   // the pointers of element el + @
   for (size_t k = 0; k < nin; ++k) step += "  const void* in" + std::to_string(k) + "_@ = (const char*)in" + std::to_string(k) + "_ + (el + @) * s_in" + std::to_string(k) + ";\n";
   const std::string keep = !carry ? "" : !bf16 ? "  _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) acc[e] = v0[e];\n"
-    : "  _Pragma(\"unroll\") for (int e = 0; e < 4; ++e) { const unsigned int pk = f2bf_pk(v0[2 * e], v0[2 * e + 1]); acc[2 * e] = __uint_as_float(pk << 16); acc[2 * e + 1] = __uint_as_float(pk & 0xffff0000u); }\n";
+    : "  _Pragma(\"unroll\") for (int e = 0; e < 4; ++e) { const unsigned int pk = f2bf_pk(v0[2 * e], v0[2 * e + 1]); acc[2 * e] = daz(__uint_as_float(pk << 16)); acc[2 * e + 1] = daz(__uint_as_float(pk & 0xffff0000u)); }\n";
   const auto at = [](std::string text, int u) { std::replace(text.begin(), text.end(), '@', (char)('0' + u)); return text; };
   const auto loop = [&](const char* end) {
     std::string l = std::string("  for (; el + ") + std::to_string(kAccAhead) + " <= " + end + "; el += " + std::to_string(kAccAhead) + ") {\n";
@@ -454,7 +455,7 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
     } else {
       const std::string idx = bc == 1 ? ("j * " + std::to_string(ch.ld) + "LL") : std::string("0");
       if (ch.type == LIBXSMM_DATATYPE_F32) std::snprintf(buf, sizeof(buf), "  float %s[8]; { const float s = ((GM const float*)in%d%s)[%s]; _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) %s[e] = s; }\n", name.c_str(), k, U, idx.c_str(), name.c_str());
-      else std::snprintf(buf, sizeof(buf), "  float %s[8]; { const float s = __uint_as_float((unsigned int)((GM const unsigned short*)in%d%s)[%s] << 16); _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) %s[e] = s; }\n", name.c_str(), k, U, idx.c_str(), name.c_str());
+      else std::snprintf(buf, sizeof(buf), "  float %s[8]; { const float s = daz(__uint_as_float((unsigned int)((GM const unsigned short*)in%d%s)[%s] << 16)); _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) %s[e] = s; }\n", name.c_str(), k, U, idx.c_str(), name.c_str());
     }
     (acc_form ? loads : body) += buf;
     return true;
@@ -499,7 +500,7 @@ bool generate_fused(const Equation& e, const libxsmm_meqn_arg_shape& out, int eq
       const int k = slot_of_arg(nd);
       if (k < 0) return false;
       phases += nd.type == LIBXSMM_DATATYPE_F32 ? "  const float " + name + " = ((GM const float*)in" + std::to_string(k) + ")[0];\n"
-                                                : "  const float " + name + " = __uint_as_float((unsigned int)((GM const unsigned short*)in" + std::to_string(k) + ")[0] << 16);\n";
+                                                : "  const float " + name + " = daz(__uint_as_float((unsigned int)((GM const unsigned short*)in" + std::to_string(k) + ")[0] << 16));\n";
       return true;
     }
     if (nd.dtype != LIBXSMM_DATATYPE_F32) return false;
