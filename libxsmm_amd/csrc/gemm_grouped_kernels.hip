@@ -59,8 +59,7 @@ const char* gemm_grouped_kernel_name(int bf16) { return bf16 ? "gemm_grouped_bf1
 
 int launch_gemm_grouped(const GemmGroupDesc* table, int ngroups, unsigned long long items, int bf16, void* stream) {
   if (ngroups <= 0 || items == 0) return 0;
-  // one wave per item up to 32 768 workgroups (16 rounds of the chip's resident waves); beyond that the waves grid-stride
-  const unsigned int grid = (unsigned int)std::min<unsigned long long>((items + 3) / 4, 32768ull);
+  const unsigned int grid = group_grid(items);
   hipStream_t st = (hipStream_t)stream;
   if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_kernel, dim3(grid), dim3(256), 0, st, table, ngroups, items);
   else hipLaunchKernelGGL(gemm_grouped_f32_kernel, dim3(grid), dim3(256), 0, st, table, ngroups, items);
@@ -72,7 +71,7 @@ int launch_gemm_grouped_inline(const GemmGroupDesc* host_table, int ngroups, uns
   GroupedInline tab;
   std::memset(&tab, 0, sizeof(tab));
   std::memcpy(tab.g, host_table, (size_t)ngroups * sizeof(GemmGroupDesc));
-  const unsigned int grid = (unsigned int)std::min<unsigned long long>((items + 3) / 4, 32768ull);
+  const unsigned int grid = group_grid(items);
   hipStream_t st = (hipStream_t)stream;
   if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);
   else hipLaunchKernelGGL(gemm_grouped_f32_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);

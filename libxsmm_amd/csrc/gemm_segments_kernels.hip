@@ -1,4 +1,4 @@
-// gemm_segments_kernels.hip -- libxsmm_hip_gemm_batch_reduce_segments: ADDRESS batch-reduce products with a reduce count of their own per C block, one launch.
+// gemm_segments_kernels.hip -- libxsmm_hip_gemm_batch_reduce_segments and its ext / offsets siblings: batch-reduce products with a reduce count of their own per C block, one launch.
 //
 // Segment s sums the products a_list[r] * b_list[r], seg_ptr[s] <= r < seg_ptr[s + 1], into c_list[s] [ref: src/generator_gemm_reference_impl.c:490-498: the
 // count and the two pointer lists are read per call].  A work item is (segment, C tile): item = segment * tiles + tile.  Every wave owns one item at a time and
@@ -11,20 +11,23 @@
 // Block pointers are only known to be element-aligned: 16- / 8-byte loads of B columns and 4-byte loads of VNNI A pairs are chosen per product by a
 // wave-uniform test of the pointer, the element-wise loads remain for every other product.
 //
-// libxsmm_hip_gemm_ext_batch_reduce_segments runs the same items through gemm_segments_f32_fused_kernel / _bf16_fused_kernel: the tiles take a FusedEpilogue
-// (gemm_group_tile.hpp) whose bias and mask pointers are d_list[s] and mask_list[s], read like c_list[s]; the operators are wave-uniform runtime bits of a small
-// by-value block (GemmSegEpilogue) next to the GemmGroupDesc.  A segment of count 0 stores the activation of its start value (the bias, bias + C) and its mask.
-// The plain kernels above are instantiated with the default epilogue and are instruction for instruction what they were without it.
-//
-// libxsmm_hip_gemm_batch_reduce_segments_offsets runs the same items through gemm_segments_offs_f32_kernel / _bf16_kernel / _f64_kernel: OFFSET batch-reduce
-// [ref: src/generator_gemm_reference_impl.c:509-513, :186-188].  The three bases travel by value in the GemmGroupDesc's operand slots; a_offs / b_offs / c_offs
-// hold signed byte offsets, read with the scalar loads that read the pointer lists above (OffsetChain), one 64-bit add per product.  A and / or B may be
-// transposed -- the backward passes of a block-sparse layer, dX = W^T dY and dW = dY X^T -- through the transposed load forms of the tiles.  The two transposes
-// are template parameters of the kernels, four instances per class: as wave-uniform runtime bits that select the tile instance inside ONE kernel they cost
-// 196 / 224 / 88 registers (f32 / bf16 / f64: a wave per SIMD less for f32, two less for f64), although no single form needs more than the ADDRESS kernels'
-// 160 / 196 / 72 -- the register allocator does not keep the four bodies apart (DESIGN.md section 9.2 has the numbers).
+// The four entries differ in two things only, and each is a policy of the one item loop (segments_items):
+//   where a segment's blocks lie       ListSource: c_list[s] and a ListChain over a_list / b_list.  OffsetSource (libxsmm_hip_gemm_batch_reduce_segments_offsets):
+//                                      OFFSET batch-reduce [ref: src/generator_gemm_reference_impl.c:509-513, :186-188], g.c + c_offs[s] and an OffsetChain -- the three
+//                                      bases travel by value in the GemmGroupDesc's operand slots, the lists hold signed byte offsets, read with the scalar loads that
+//                                      read the pointer lists, one 64-bit add per product.
+//   where its epilogue pointers lie    none (NoEpilogue: every use of it in the tiles sits behind `if constexpr`), or the FusedEpilogue of the two ext entries
+//                                      [ref: src/generator_gemm_reference_impl.c:294-372] -- column bias, ReLU (+ bitmask), sigmoid -- whose bias and mask blocks are
+//                                      d_list[s] / mask_list[s] (GemmSegEpilogue) or d + d_offs[s] / mask + mask_offs[s] (GemmSegOffsEpilogue); without a bias list the one
+//                                      `d` is shared.  The entries are wave-uniform and read like C's; the operators are wave-uniform runtime bits of the by-value
+//                                      block next to the GemmGroupDesc.  A segment of count 0 stores the activation of its start value (the bias, bias + C) and its
+//                                      mask.  The mask bytes leave through vector stores (acc_relu_mask: a whole byte when its 8 rows are valid, read-merge-write for
+//                                      the byte that holds row m - 1).
+// With offsets A and / or B may be transposed -- the backward passes of a block-sparse layer, dX = W^T dY and dW = dY X^T -- through the transposed load forms of
+// the tiles.  The two transposes are template parameters of the kernels, four instances per class: as wave-uniform runtime bits that select the tile instance
+// inside ONE kernel they cost 196 / 224 / 88 registers (f32 / bf16 / f64: a wave per SIMD less for f32, two less for f64), although no single form needs more
+// than the ADDRESS kernels' 160 / 196 / 72 -- the register allocator does not keep the four bodies apart (DESIGN.md section 9.2 has the numbers).
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include "internal.hpp"
 #include "gemm_device.hpp"
 #include "bf16_cvt.hpp"
@@ -34,71 +37,65 @@ namespace xamd {
 
 using namespace group_tile;
 
-// CLS: 0 f32, 1 bf16, 2 f64.  FUSED: the ext ABI's epilogue per segment (libxsmm_hip_gemm_ext_batch_reduce_segments); d_list[s] and mask_list[s] are wave-uniform
-// like c_list[s] and are read the same way.
-template <int CLS, bool FUSED = false>
-__device__ __forceinline__ void segments_body(const GemmGroupDesc& g, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list,
-  void* const* c_list, unsigned long long total, const GemmSegEpilogue* ep = nullptr) {
-  const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const unsigned int lane = threadIdx.x & 63u;
-  const unsigned long long step = (unsigned long long)gridDim.x * 4u;
-  const unsigned int tiles = (unsigned int)(g.tiles_m * g.tiles_n);
-  for (unsigned long long item = (unsigned long long)blockIdx.x * 4u + wave; item < total; item += step) {
-    unsigned long long s = item; unsigned int t = 0;
-    if (tiles != 1) { s = item / tiles; t = (unsigned int)(item - s * tiles); }
-    const unsigned int tn = t / (unsigned int)g.tiles_m, tm = t - tn * (unsigned int)g.tiles_m;
-    const unsigned long long r0 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s]), r1 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s + 1]);
-    gptr c = (gptr)list_entry((const void*)c_list, s);
-    const ListChain ch{(const void*)(a_list + r0), (const void*)(b_list + r0), r1 - r0, g.a_vec4, g.b_vec16, g.b_vec8};
-    if constexpr (FUSED) {
-      FusedEpilogue e{(gcptr)ep->d, nullptr, ep->colbias, ep->act, ep->mask_ld};
-      if (ep->colbias && ep->d_list) e.d = list_entry((const void*)ep->d_list, s);
-      if (ep->act == 2) e.mask = (GM unsigned char*)list_entry((const void*)ep->mask_list, s);
-      if (g.tile == 32) {
-        if constexpr (CLS == 1) tile_bf16<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane, e); else tile_f32<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane, e);
-      } else {
-        if constexpr (CLS == 1) tile_bf16<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane, e); else tile_f32<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane, e);
-      }
-    } else if constexpr (CLS == 2) tile_f64(g, ch, c, (int)tm * 16, (int)tn * 16, lane);
-    else if (g.tile == 32) {
-      if constexpr (CLS == 1) tile_bf16<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane); else tile_f32<32, true>(g, ch, c, (int)tm * 32, (int)tn * 32, lane);
-    } else {
-      if constexpr (CLS == 1) tile_bf16<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane); else tile_f32<16, true>(g, ch, c, (int)tm * 16, (int)tn * 16, lane);
-    }
+// A SOURCE says where the blocks of segment s lie: c(g, s) is its C block -- one scalar load -- and chain(g, r0, r1) the chain over its products (constructing
+// a chain loads nothing).  ListSource reads three pointer lists, OffsetSource adds signed byte offsets to the three bases in g.a / g.b / g.c.
+struct ListSource {
+  const void* const* a_list; const void* const* b_list; void* const* c_list;
+  __device__ __forceinline__ gptr c(const GemmGroupDesc&, unsigned long long s) const { return (gptr)list_entry((const void*)c_list, s); }
+  __device__ __forceinline__ ListChain chain(const GemmGroupDesc& g, unsigned long long r0, unsigned long long r1) const {
+    return ListChain{(const void*)(a_list + r0), (const void*)(b_list + r0), r1 - r0, g.a_vec4, g.b_vec16, g.b_vec8};
   }
-}
+};
+// a_wide: bit 0 / 1: the rows of a transposed A are multiples of 16 / 8 bytes apart (OffsetChain::va16 / va8).  Wide is how the kernel holds it: `int` for a
+// parameter of its own, `const int&` for a field of the by-value epilogue block, read where the chain is built.
+template <typename Wide> struct OffsetSource {
+  const long long* a_offs; const long long* b_offs; const long long* c_offs; Wide a_wide;
+  __device__ __forceinline__ gptr c(const GemmGroupDesc& g, unsigned long long s) const { return (gptr)g.c + (long long)uniform_u64(((GM const unsigned long long*)c_offs)[s]); }
+  __device__ __forceinline__ OffsetChain chain(const GemmGroupDesc& g, unsigned long long r0, unsigned long long r1) const {
+    return OffsetChain{(gcptr)g.a, (gcptr)g.b, (const void*)(a_offs + r0), (const void*)(b_offs + r0), r1 - r0, g.a_vec4, g.b_vec16, g.b_vec8, a_wide & 1, (a_wide >> 1) & 1};
+  }
+};
 
-__global__ __launch_bounds__(256) void gemm_segments_f32_kernel(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list,
-  const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { segments_body<0>(g, seg_ptr, a_list, b_list, c_list, total); }
-__global__ __launch_bounds__(256) void gemm_segments_bf16_kernel(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list,
-  const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { segments_body<1>(g, seg_ptr, a_list, b_list, c_list, total); }
-__global__ __launch_bounds__(256) void gemm_segments_f64_kernel(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list,
-  const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { segments_body<2>(g, seg_ptr, a_list, b_list, c_list, total); }
+// A SEGMENT EPILOGUE says where the FusedEpilogue pointers of segment s come from: nowhere (the plain kernels: NoEpilogue), d_list[s] / mask_list[s], or
+// d + d_offs[s] / mask + mask_offs[s]; without a bias list the one `d` is shared by every segment.  The entries are wave-uniform and read like C's.
+struct NoSegEpilogue {
+  __device__ __forceinline__ NoEpilogue at(unsigned long long) const { return NoEpilogue(); }
+};
+struct ListSegEpilogue {
+  const GemmSegEpilogue& ep;
+  __device__ __forceinline__ FusedEpilogue at(unsigned long long s) const {
+    FusedEpilogue e{(gcptr)ep.d, nullptr, ep.colbias, ep.act, ep.mask_ld};
+    if (ep.colbias && ep.d_list) e.d = list_entry((const void*)ep.d_list, s);
+    if (ep.act == 2) e.mask = (GM unsigned char*)list_entry((const void*)ep.mask_list, s);
+    return e;
+  }
+};
+struct OffsetSegEpilogue {
+  const GemmSegOffsEpilogue& ep;
+  __device__ __forceinline__ FusedEpilogue at(unsigned long long s) const {
+    FusedEpilogue e{(gcptr)ep.d, nullptr, ep.colbias, ep.act, ep.mask_ld};
+    if (ep.colbias && ep.d_offs) e.d += (long long)uniform_u64(((GM const unsigned long long*)ep.d_offs)[s]);
+    if (ep.act == 2) e.mask = (GM unsigned char*)ep.mask + (long long)uniform_u64(((GM const unsigned long long*)ep.mask_offs)[s]);
+    return e;
+  }
+};
 
-__global__ __launch_bounds__(256) void gemm_segments_f32_fused_kernel(GemmGroupDesc g, GemmSegEpilogue e, const unsigned long long* __restrict__ seg_ptr,
-  const void* const* __restrict__ a_list, const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) {
-  segments_body<0, true>(g, seg_ptr, a_list, b_list, c_list, total, &e);
-}
-__global__ __launch_bounds__(256) void gemm_segments_bf16_fused_kernel(GemmGroupDesc g, GemmSegEpilogue e, const unsigned long long* __restrict__ seg_ptr,
-  const void* const* __restrict__ a_list, const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) {
-  segments_body<1, true>(g, seg_ptr, a_list, b_list, c_list, total, &e);
-}
-
-// a_wide: bit 0 / 1: the rows of a transposed A are multiples of 16 / 8 bytes apart (OffsetChain::va16 / va8)
-template <int CLS, bool TA, bool TB>
-__device__ __forceinline__ void segments_offs_tile(const GemmGroupDesc& g, const OffsetChain& ch, gptr c, int tm, int tn, unsigned int lane) {
-  if constexpr (CLS == 2) tile_f64<OffsetChain, TA, TB>(g, ch, c, tm * 16, tn * 16, lane);
+// CLS: 0 f32, 1 bf16, 2 f64 (16 x 16 tiles only, no epilogue).  The tile edge is a wave-uniform runtime value, the class and the transposes pick the instance.
+template <int CLS, bool TA, bool TB, typename Chain, typename Epi>
+__device__ __forceinline__ void segment_tile(const GemmGroupDesc& g, const Chain& ch, gptr c, int tm, int tn, unsigned int lane, const Epi& e) {
+  if constexpr (CLS == 2) tile_f64<Chain, TA, TB>(g, ch, c, tm * 16, tn * 16, lane);
   else if (g.tile == 32) {
-    if constexpr (CLS == 1) tile_bf16<32, true, OffsetChain, NoEpilogue, TA, TB>(g, ch, c, tm * 32, tn * 32, lane);
-    else tile_f32<32, true, OffsetChain, NoEpilogue, TA, TB>(g, ch, c, tm * 32, tn * 32, lane);
+    if constexpr (CLS == 1) tile_bf16<32, true, Chain, Epi, TA, TB>(g, ch, c, tm * 32, tn * 32, lane, e);
+    else tile_f32<32, true, Chain, Epi, TA, TB>(g, ch, c, tm * 32, tn * 32, lane, e);
   } else {
-    if constexpr (CLS == 1) tile_bf16<16, true, OffsetChain, NoEpilogue, TA, TB>(g, ch, c, tm * 16, tn * 16, lane);
-    else tile_f32<16, true, OffsetChain, NoEpilogue, TA, TB>(g, ch, c, tm * 16, tn * 16, lane);
+    if constexpr (CLS == 1) tile_bf16<16, true, Chain, Epi, TA, TB>(g, ch, c, tm * 16, tn * 16, lane, e);
+    else tile_f32<16, true, Chain, Epi, TA, TB>(g, ch, c, tm * 16, tn * 16, lane, e);
   }
 }
-template <int CLS, bool TA, bool TB>
-__device__ __forceinline__ void segments_offs_body(const GemmGroupDesc& g, int a_wide, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs,
-  const long long* c_offs, unsigned long long total) {
+
+// The item loop of all 25 kernels.  Per item, in this order: seg_ptr[s], seg_ptr[s + 1], C's address, the epilogue's entries, then the chain.
+template <int CLS, bool TA, bool TB, typename Source, typename SegEpilogue>
+__device__ __forceinline__ void segments_items(const GemmGroupDesc& g, const unsigned long long* seg_ptr, Source src, SegEpilogue sep, unsigned long long total) {
   const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const unsigned int lane = threadIdx.x & 63u;
   const unsigned long long step = (unsigned long long)gridDim.x * 4u;
@@ -108,75 +105,93 @@ __device__ __forceinline__ void segments_offs_body(const GemmGroupDesc& g, int a
     if (tiles != 1) { s = item / tiles; t = (unsigned int)(item - s * tiles); }
     const unsigned int tn = t / (unsigned int)g.tiles_m, tm = t - tn * (unsigned int)g.tiles_m;
     const unsigned long long r0 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s]), r1 = uniform_u64(((GM const unsigned long long*)seg_ptr)[s + 1]);
-    gptr c = (gptr)g.c + (long long)uniform_u64(((GM const unsigned long long*)c_offs)[s]);
-    const OffsetChain ch{(gcptr)g.a, (gcptr)g.b, (const void*)(a_offs + r0), (const void*)(b_offs + r0), r1 - r0, g.a_vec4, g.b_vec16, g.b_vec8, a_wide & 1, (a_wide >> 1) & 1};
-    segments_offs_tile<CLS, TA, TB>(g, ch, c, (int)tm, (int)tn, lane);
+    gptr c = src.c(g, s);
+    const auto e = sep.at(s);
+    const auto ch = src.chain(g, r0, r1);
+    segment_tile<CLS, TA, TB>(g, ch, c, (int)tm, (int)tn, lane, e);
   }
 }
+
+#define XAMD_SEG_KERNEL(NAME, CLS) \
+  __global__ __launch_bounds__(256) void NAME(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list, \
+    const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { \
+    segments_items<CLS, false, false>(g, seg_ptr, ListSource{a_list, b_list, c_list}, NoSegEpilogue{}, total); }
+XAMD_SEG_KERNEL(gemm_segments_f32_kernel, 0)
+XAMD_SEG_KERNEL(gemm_segments_bf16_kernel, 1)
+XAMD_SEG_KERNEL(gemm_segments_f64_kernel, 2)
+#undef XAMD_SEG_KERNEL
+
+#define XAMD_SEG_FUSED_KERNEL(NAME, CLS) \
+  __global__ __launch_bounds__(256) void NAME(GemmGroupDesc g, GemmSegEpilogue e, const unsigned long long* __restrict__ seg_ptr, \
+    const void* const* __restrict__ a_list, const void* const* __restrict__ b_list, void* const* __restrict__ c_list, unsigned long long total) { \
+    segments_items<CLS, false, false>(g, seg_ptr, ListSource{a_list, b_list, c_list}, ListSegEpilogue{e}, total); }
+XAMD_SEG_FUSED_KERNEL(gemm_segments_f32_fused_kernel, 0)
+XAMD_SEG_FUSED_KERNEL(gemm_segments_bf16_fused_kernel, 1)
+#undef XAMD_SEG_FUSED_KERNEL
 
 #define XAMD_OFFS_KERNEL(NAME, CLS) \
   template <bool TA, bool TB> __global__ __launch_bounds__(256) void NAME(GemmGroupDesc g, int a_wide, const unsigned long long* __restrict__ seg_ptr, \
     const long long* __restrict__ a_offs, const long long* __restrict__ b_offs, const long long* __restrict__ c_offs, unsigned long long total) { \
-    segments_offs_body<CLS, TA, TB>(g, a_wide, seg_ptr, a_offs, b_offs, c_offs, total); }
+    segments_items<CLS, TA, TB>(g, seg_ptr, OffsetSource<int>{a_offs, b_offs, c_offs, a_wide}, NoSegEpilogue{}, total); }
 XAMD_OFFS_KERNEL(gemm_segments_offs_f32_kernel, 0)
 XAMD_OFFS_KERNEL(gemm_segments_offs_bf16_kernel, 1)
 XAMD_OFFS_KERNEL(gemm_segments_offs_f64_kernel, 2)
 #undef XAMD_OFFS_KERNEL
 
-const char* gemm_segments_kernel_name(int cls) { return cls == 2 ? "gemm_segments_f64_kernel" : (cls == 1 ? "gemm_segments_bf16_kernel" : "gemm_segments_f32_kernel"); }
+#define XAMD_OFFS_FUSED_KERNEL(NAME, CLS) \
+  template <bool TA, bool TB> __global__ __launch_bounds__(256) void NAME(GemmGroupDesc g, GemmSegOffsEpilogue e, const unsigned long long* __restrict__ seg_ptr, \
+    const long long* __restrict__ a_offs, const long long* __restrict__ b_offs, const long long* __restrict__ c_offs, unsigned long long total) { \
+    segments_items<CLS, TA, TB>(g, seg_ptr, OffsetSource<const int&>{a_offs, b_offs, c_offs, e.a_wide}, OffsetSegEpilogue{e}, total); }
+XAMD_OFFS_FUSED_KERNEL(gemm_segments_offs_f32_fused_kernel, 0)
+XAMD_OFFS_FUSED_KERNEL(gemm_segments_offs_bf16_fused_kernel, 1)
+#undef XAMD_OFFS_FUSED_KERNEL
 
-int launch_gemm_segments(const GemmGroupDesc& g, int cls, unsigned long long items, const unsigned long long* seg_ptr, const void* const* a_list,
-  const void* const* b_list, void* const* c_list, void* stream) {
-  if (items == 0) return 0;
-  // one wave per item up to 32 768 workgroups (16 rounds of the chip's resident waves); beyond that the waves grid-stride
-  const unsigned int grid = (unsigned int)std::min<unsigned long long>((items + 3) / 4, 32768ull);
-  hipStream_t st = (hipStream_t)stream;
-  if (cls == 2) hipLaunchKernelGGL(gemm_segments_f64_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
-  else if (cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
-  else hipLaunchKernelGGL(gemm_segments_f32_kernel, dim3(grid), dim3(256), 0, st, g, seg_ptr, a_list, b_list, c_list, items);
-  return (int)hipGetLastError();
-}
-
-const char* gemm_segments_fused_kernel_name(int cls) { return cls == 1 ? "gemm_segments_bf16_fused_kernel" : "gemm_segments_f32_fused_kernel"; }
-
-int launch_gemm_segments_fused(const GemmGroupDesc& g, const GemmSegEpilogue& e, int cls, unsigned long long items, const unsigned long long* seg_ptr,
-  const void* const* a_list, const void* const* b_list, void* const* c_list, void* stream) {
-  if (items == 0) return 0;
-  const unsigned int grid = (unsigned int)std::min<unsigned long long>((items + 3) / 4, 32768ull);     // the plain launch's rule
-  hipStream_t st = (hipStream_t)stream;
-  if (cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, g, e, seg_ptr, a_list, b_list, c_list, items);
-  else hipLaunchKernelGGL(gemm_segments_f32_fused_kernel, dim3(grid), dim3(256), 0, st, g, e, seg_ptr, a_list, b_list, c_list, items);
-  return (int)hipGetLastError();
-}
-
-// forms: bit 0 TRANS_A, bit 1 TRANS_B (the kernel instance); bits 2 / 3: a_wide
-const char* gemm_segments_offs_kernel_name(int cls, int forms) {
-  static const char* const names[3][4] = {
-    {"gemm_segments_offs_f32_kernel<0,0>", "gemm_segments_offs_f32_kernel<1,0>", "gemm_segments_offs_f32_kernel<0,1>", "gemm_segments_offs_f32_kernel<1,1>"},
-    {"gemm_segments_offs_bf16_kernel<0,0>", "gemm_segments_offs_bf16_kernel<1,0>", "gemm_segments_offs_bf16_kernel<0,1>", "gemm_segments_offs_bf16_kernel<1,1>"},
-    {"gemm_segments_offs_f64_kernel<0,0>", "gemm_segments_offs_f64_kernel<1,0>", "gemm_segments_offs_f64_kernel<0,1>", "gemm_segments_offs_f64_kernel<1,1>"}};
-  return names[cls][forms & 3];
-}
+// the four instances of an offsets kernel, indexed by forms & 3 (bit 0 TRANS_A, bit 1 TRANS_B)
+#define XAMD_FORMS(NAME) {NAME "<0,0>", NAME "<1,0>", NAME "<0,1>", NAME "<1,1>"}
+static const char* const kListNames[5] = {"gemm_segments_f32_kernel", "gemm_segments_bf16_kernel", "gemm_segments_f64_kernel", "gemm_segments_f32_fused_kernel",
+  "gemm_segments_bf16_fused_kernel"};
+static const char* const kOffsNames[5][4] = {XAMD_FORMS("gemm_segments_offs_f32_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_kernel"), XAMD_FORMS("gemm_segments_offs_f64_kernel"),
+  XAMD_FORMS("gemm_segments_offs_f32_fused_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_fused_kernel")};
+#undef XAMD_FORMS
 
 template <bool TA, bool TB>
-static void launch_offs_form(const GemmGroupDesc& g, int a_wide, int cls, unsigned int grid, hipStream_t st, unsigned long long items, const unsigned long long* seg_ptr,
-  const long long* a_offs, const long long* b_offs, const long long* c_offs) {
-  if (cls == 2) hipLaunchKernelGGL((gemm_segments_offs_f64_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, seg_ptr, a_offs, b_offs, c_offs, items);
-  else if (cls == 1) hipLaunchKernelGGL((gemm_segments_offs_bf16_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, seg_ptr, a_offs, b_offs, c_offs, items);
-  else hipLaunchKernelGGL((gemm_segments_offs_f32_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, seg_ptr, a_offs, b_offs, c_offs, items);
+static void launch_offs_form(const SegmentsLaunch& l, unsigned int grid, hipStream_t st) {
+  const long long* a_offs = (const long long*)l.a_list; const long long* b_offs = (const long long*)l.b_list; const long long* c_offs = (const long long*)l.c_list;
+  if (l.fused) {
+    const GemmSegOffsEpilogue& e = *(const GemmSegOffsEpilogue*)l.epilogue;
+    if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_bf16_fused_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
+    else hipLaunchKernelGGL((gemm_segments_offs_f32_fused_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
+    return;
+  }
+  const int a_wide = (l.forms >> 2) & 3;
+  if (l.cls == 2) hipLaunchKernelGGL((gemm_segments_offs_f64_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
+  else if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_bf16_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
+  else hipLaunchKernelGGL((gemm_segments_offs_f32_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
 }
 
-int launch_gemm_segments_offs(const GemmGroupDesc& g, int forms, int cls, unsigned long long items, const unsigned long long* seg_ptr, const long long* a_offs,
-  const long long* b_offs, const long long* c_offs, void* stream) {
-  if (items == 0) return 0;
-  const unsigned int grid = (unsigned int)std::min<unsigned long long>((items + 3) / 4, 32768ull);     // the plain launch's rule
+static void launch_list(const SegmentsLaunch& l, unsigned int grid, hipStream_t st) {
+  const void* const* a_list = (const void* const*)l.a_list; const void* const* b_list = (const void* const*)l.b_list; void* const* c_list = (void* const*)l.c_list;
+  if (l.fused) {
+    const GemmSegEpilogue& e = *(const GemmSegEpilogue*)l.epilogue;
+    if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
+    else hipLaunchKernelGGL(gemm_segments_f32_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
+  } else if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_f64_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+  else if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+  else hipLaunchKernelGGL(gemm_segments_f32_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+}
+
+int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname) {
+  const int row = l.fused ? (l.cls == 1 ? 4 : 3) : l.cls;
+  *kname = l.offsets ? kOffsNames[row][l.forms & 3] : kListNames[row];
+  if (l.items == 0) return 0;
+  const unsigned int grid = group_grid(l.items);
   hipStream_t st = (hipStream_t)stream;
-  const int a_wide = (forms >> 2) & 3;
-  switch (forms & 3) {
-    case 0: launch_offs_form<false, false>(g, a_wide, cls, grid, st, items, seg_ptr, a_offs, b_offs, c_offs); break;
-    case 1: launch_offs_form<true, false>(g, a_wide, cls, grid, st, items, seg_ptr, a_offs, b_offs, c_offs); break;
-    case 2: launch_offs_form<false, true>(g, a_wide, cls, grid, st, items, seg_ptr, a_offs, b_offs, c_offs); break;
-    default: launch_offs_form<true, true>(g, a_wide, cls, grid, st, items, seg_ptr, a_offs, b_offs, c_offs); break;
+  if (!l.offsets) launch_list(l, grid, st);
+  else switch (l.forms & 3) {
+    case 0: launch_offs_form<false, false>(l, grid, st); break;
+    case 1: launch_offs_form<true, false>(l, grid, st); break;
+    case 2: launch_offs_form<false, true>(l, grid, st); break;
+    default: launch_offs_form<true, true>(l, grid, st); break;
   }
   return (int)hipGetLastError();
 }

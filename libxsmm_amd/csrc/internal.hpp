@@ -314,25 +314,22 @@ int launch_gemm_grouped(const GemmGroupDesc* table, int ngroups, unsigned long l
 constexpr int kGroupedInline = 24;                // tables of up to this many groups travel in the kernel arguments (launch_gemm_grouped_inline: host table)
 int launch_gemm_grouped_inline(const GemmGroupDesc* host_table, int ngroups, unsigned long long items, int bf16, void* stream);
 const char* gemm_grouped_kernel_name(int bf16);
-// gemm_segments_kernels.hip (libxsmm_hip_gemm_batch_reduce_segments): `g` carries the shape, leading dimensions, beta, layout bits, tile edge and what the leading
-// dimensions allow of the wider loads (a_vec4 / b_vec16 / b_vec8); its operand, stride and prefix slots are unused.  cls: 0 f32, 1 bf16, 2 f64.  The lists are device-accessible.
-int launch_gemm_segments(const GemmGroupDesc& g, int cls, unsigned long long items, const unsigned long long* seg_ptr, const void* const* a_list,
-  const void* const* b_list, void* const* c_list, void* stream);
-const char* gemm_segments_kernel_name(int cls);
-// the same launch with the ext ABI's epilogue (column bias, ReLU (+ bitmask), sigmoid) fused into the store; cls 0 or 1
-int launch_gemm_segments_fused(const GemmGroupDesc& g, const GemmSegEpilogue& e, int cls, unsigned long long items, const unsigned long long* seg_ptr,
-  const void* const* a_list, const void* const* b_list, void* const* c_list, void* stream);
-const char* gemm_segments_fused_kernel_name(int cls);
-// libxsmm_hip_gemm_batch_reduce_segments_offsets: g.a / g.b / g.c are the three bases; forms: bit 0 TRANS_A, bit 1 TRANS_B, bit 2 / 3: lda spans a multiple of 16 / 8 bytes
-// (the wide loads of a transposed A)
-int launch_gemm_segments_offs(const GemmGroupDesc& g, int forms, int cls, unsigned long long items, const unsigned long long* seg_ptr, const long long* a_offs,
-  const long long* b_offs, const long long* c_offs, void* stream);
-const char* gemm_segments_offs_kernel_name(int cls, int forms);
-// gemm_segments_offs_fused_kernels.hip (libxsmm_hip_gemm_ext_batch_reduce_segments_offsets): the offsets launch with the fused epilogue; cls 0 or 1, forms bit 0 / 1 as
-// above (bits 2 / 3 travel in e.a_wide)
-int launch_gemm_segments_offs_fused(const GemmGroupDesc& g, const GemmSegOffsEpilogue& e, int forms, int cls, unsigned long long items, const unsigned long long* seg_ptr,
-  const long long* a_offs, const long long* b_offs, const long long* c_offs, void* stream);
-const char* gemm_segments_offs_fused_kernel_name(int cls, int forms);
+// the grid of the grouped and the segment kernels (four waves a workgroup, a wave per work item): one wave per item up to 32 768 workgroups (16 rounds of the
+// chip's resident waves); beyond that the waves grid-stride
+inline unsigned int group_grid(unsigned long long items) { return (unsigned int)((items + 3) / 4 < 32768ull ? (items + 3) / 4 : 32768ull); }
+// gemm_segments_kernels.hip: one launch of the four libxsmm_hip_gemm_*batch_reduce_segments* entries.  `g` carries the shape, leading dimensions, beta, layout
+// bits, tile edge and what the leading dimensions allow of the wider loads (a_vec4 / b_vec16 / b_vec8); its stride and prefix slots are unused.  The lists are
+// device-accessible: pointers, or (offsets) signed byte offsets from the three bases in g.a / g.b / g.c.
+struct SegmentsLaunch {
+  GemmGroupDesc g;
+  int cls, forms;                                   // cls: 0 f32, 1 bf16, 2 f64; forms (offsets): bit 0 TRANS_A, bit 1 TRANS_B, bit 2 / 3: lda spans a multiple of 16 / 8 bytes (the wide loads of a transposed A)
+  unsigned long long items;                         // segments x C tiles
+  const unsigned long long* seg_ptr;
+  const void* a_list; const void* b_list; const void* c_list;
+  bool offsets, fused;                              // fused: the ext ABI's epilogue (column bias, ReLU (+ bitmask), sigmoid) in the store; cls 0 or 1
+  const void* epilogue;                             // fused: the GemmSegEpilogue, with offsets the GemmSegOffsEpilogue
+};
+int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname);   // *kname: the kernel instance of class x forms x fused x offsets
 int launch_spmm(const SpmmArgs& args, void* stream, const char** kernel_name);
 int launch_bcsc(const BcscArgs& args, void* stream, const char** kernel_name);
 // Automatic streaming decision (libxsmm_hip_set_streaming_hint(0)): a launch whose own operands exceed the Infinity Cache streams -- and so does a launch whose operands

@@ -2255,43 +2255,55 @@ LIBXSMM_API void libxsmm_hip_meqn_batch_strided_accumulate(libxsmm_meqn_function
 // A group enters the grouped kernels (gemm_grouped_kernels.hip) when its handle is a plain GEMM or a STRIDE batch-reduce handle of f32 x f32 -> f32 or
 // bf16 x bf16 -> f32 / bf16 (A flat or VNNI-2, B flat, C not VNNI), NN, with no flag beyond beta and the hints; `cls` = 0 (f32) or 1 (bf16).
 static constexpr unsigned long long kGroupedOwnF32Items = 2048;
-static bool grouped_eligible(const KernelCtx* k, const libxsmm_hip_gemm_group& grp, GemmGroupDesc& g, int& cls) {
-  if (k->kind != K_GEMM) return false;
-  const libxsmm_gemm_descriptor& d = k->g;
-  const unsigned int f = effective_gemm_flags(d);
-  const unsigned int allowed = LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_ALIGN_A | LIBXSMM_GEMM_FLAG_ALIGN_C_NTS_HINT | LIBXSMM_GEMM_FLAG_NO_RESET_TILECONFIG |
-    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE;
-  if (f & ~allowed) return false;
+// What the grouped and the segment kernels share (gemm_group_tile.hpp), derived from a handle in one place for grouped_eligible and segments_validate: the
+// precision class, the flags every caller takes (beta, VNNI_A and the hints; `own`: the batch-reduce kind, transposes and ABI bits of the caller), the bound of
+// the kernels' 32-bit element offsets, and the GemmGroupDesc fields that depend on the descriptor alone.  Returns the first check that fails, in this order;
+// the callers say what that means (grouped: the group runs on its own; segments: an error).  The operands, strides and wide-load bits stay with the callers.
+static constexpr unsigned int kGroupTileFlags = LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_ALIGN_A | LIBXSMM_GEMM_FLAG_ALIGN_C_NTS_HINT | LIBXSMM_GEMM_FLAG_NO_RESET_TILECONFIG |
+  LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI;
+enum GroupShape { kGroupShapeOk = 0, kGroupShapeTypes, kGroupShapeFlags, kGroupShapeLd };
+static GroupShape group_shape(const libxsmm_gemm_descriptor& d, unsigned int f, unsigned int own, GemmGroupDesc& g, int& cls) {
   const bool f32 = d.a_type == LIBXSMM_DATATYPE_F32 && d.b_type == LIBXSMM_DATATYPE_F32 && d.c_type == LIBXSMM_DATATYPE_F32;
+  const bool f64 = d.a_type == LIBXSMM_DATATYPE_F64 && d.b_type == LIBXSMM_DATATYPE_F64 && d.c_type == LIBXSMM_DATATYPE_F64;
   const bool bf16 = d.a_type == LIBXSMM_DATATYPE_BF16 && d.b_type == LIBXSMM_DATATYPE_BF16 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF16);
-  if (!f32 && !bf16) return false;
-  const libxsmm_gemm_param& p = grp.param;
-  if (d.m == 0 || d.n == 0 || d.k == 0 || !p.a.primary || !p.b.primary || !p.c.primary) return false;
-  unsigned long long brc = 1;
-  if (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) { brc = *(const unsigned long long*)p.op.tertiary; if (brc == 0) return false; }
-  // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers)
+  if (!f32 && !f64 && !bf16) return kGroupShapeTypes;
+  cls = f64 ? 2 : (bf16 ? 1 : 0);
+  if (f & ~(kGroupTileFlags | own)) return kGroupShapeFlags;
+  // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers); a transposed operand spans lda x m / ldb x k
+  const bool ta = (f & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (f & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
   const unsigned long long lim = 1ull << 31;
-  if ((unsigned long long)d.lda * (d.k + 1) >= lim || (unsigned long long)d.ldb * d.n >= lim || (unsigned long long)d.ldc * d.n >= lim) return false;
-  const int tile = (d.m <= 16 && d.n <= 16) ? 16 : 32;
-  const unsigned long long tiles = (unsigned long long)((d.m + tile - 1) / tile) * ((d.n + tile - 1) / tile);
-  if (grp.count * tiles >= (1ull << 32)) return false;             // the kernels decode a group's items with 32-bit divisions
+  if ((unsigned long long)d.lda * (ta ? d.m : d.k + 1) >= lim || (unsigned long long)d.ldb * (tb ? d.k : d.n) >= lim || (unsigned long long)d.ldc * d.n >= lim) return kGroupShapeLd;
+  const int tile = (f64 || (d.m <= 16 && d.n <= 16)) ? 16 : 32;
   std::memset(&g, 0, sizeof(g));
-  g.a = (const char*)p.a.primary; g.b = (const char*)p.b.primary; g.c = (char*)p.c.primary;
-  g.sa = grp.stride_a; g.sb = grp.stride_b; g.sc = grp.stride_c;
-  g.br_sa = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_a : 0; g.br_sb = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_b : 0;
-  g.br_count = brc;
   g.m = (int)d.m; g.n = (int)d.n; g.k = (int)d.k; g.lda = (int)d.lda; g.ldb = (int)d.ldb; g.ldc = (int)d.ldc;
   g.tile = tile; g.tiles_m = (int)((d.m + tile - 1) / tile); g.tiles_n = (int)((d.n + tile - 1) / tile);
   g.beta1 = (f & LIBXSMM_GEMM_FLAG_BETA_0) ? 0 : 1;
   g.vnni_a = (bf16 && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
   g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
+  return kGroupShapeOk;
+}
+static bool grouped_eligible(const KernelCtx* k, const libxsmm_hip_gemm_group& grp, GemmGroupDesc& g, int& cls) {
+  if (k->kind != K_GEMM) return false;
+  const libxsmm_gemm_descriptor& d = k->g;
+  const unsigned int f = effective_gemm_flags(d);
+  if (group_shape(d, f, LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE, g, cls) != kGroupShapeOk || cls == 2) return false;
+  const libxsmm_gemm_param& p = grp.param;
+  if (d.m == 0 || d.n == 0 || d.k == 0 || !p.a.primary || !p.b.primary || !p.c.primary) return false;
+  unsigned long long brc = 1;
+  if (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) { brc = *(const unsigned long long*)p.op.tertiary; if (brc == 0) return false; }
+  const unsigned long long tiles = (unsigned long long)g.tiles_m * (unsigned long long)g.tiles_n;
+  if (grp.count * tiles >= (1ull << 32)) return false;             // the kernels decode a group's items with 32-bit divisions
+  g.a = (const char*)p.a.primary; g.b = (const char*)p.b.primary; g.c = (char*)p.c.primary;
+  g.sa = grp.stride_a; g.sb = grp.stride_b; g.sc = grp.stride_c;
+  g.br_sa = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_a : 0; g.br_sb = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_b : 0;
+  g.br_count = brc;
+  // the wider loads hold for every element and every block of the group: the base and the strides decide
   const unsigned long long ua = (unsigned long long)(uintptr_t)g.a | (unsigned long long)g.sa | (unsigned long long)g.br_sa;
-  const unsigned long long ub = (unsigned long long)(uintptr_t)g.b | (unsigned long long)g.sb | (unsigned long long)g.br_sb | ((unsigned long long)d.ldb * (bf16 ? 2 : 4));
-  g.a_vec4 = (bf16 && (ua & 3) == 0) ? 1 : 0;
+  const unsigned long long ub = (unsigned long long)(uintptr_t)g.b | (unsigned long long)g.sb | (unsigned long long)g.br_sb | ((unsigned long long)d.ldb * (cls == 1 ? 2 : 4));
+  g.a_vec4 = (cls == 1 && (ua & 3) == 0) ? 1 : 0;
   g.b_vec16 = (ub & 15) == 0 ? 1 : 0;
   g.b_vec8 = (ub & 7) == 0 ? 1 : 0;
   g.first = grp.count * tiles;                          // (the item count: turned into the exclusive prefix when the table is complete)
-  cls = bf16 ? 1 : 0;
   return true;
 }
 LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* groups, size_t ngroups) {
@@ -2389,41 +2401,25 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
   if (!offsets && !(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS)) {
     set_error(-3, "%s: handle is not an ADDRESS batch-reduce kernel (%s with LIBXSMM_GEMM_BATCH_REDUCE_ADDRESS)", fn, ext ? "libxsmm_dispatch_brgemm_ext" : "libxsmm_dispatch_brgemm"); return nullptr;
   }
-  const bool f32 = d.a_type == LIBXSMM_DATATYPE_F32 && d.b_type == LIBXSMM_DATATYPE_F32 && d.c_type == LIBXSMM_DATATYPE_F32;
-  const bool f64 = d.a_type == LIBXSMM_DATATYPE_F64 && d.b_type == LIBXSMM_DATATYPE_F64 && d.c_type == LIBXSMM_DATATYPE_F64;
-  const bool bf16 = d.a_type == LIBXSMM_DATATYPE_BF16 && d.b_type == LIBXSMM_DATATYPE_BF16 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF16);
-  if (!f32 && !f64 && !bf16) {
+  const unsigned int f = effective_gemm_flags(d);
+  const unsigned int own = (offsets ? (unsigned int)(LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B) : (unsigned int)LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS) |
+    (ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
+  const GroupShape shape = group_shape(d, f, own, g, cls);
+  if (shape == kGroupShapeTypes) {
     set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return nullptr;
   }
-  const unsigned int f = effective_gemm_flags(d);
   const bool ta = (f & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (f & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
   if (!offsets && (ta || tb)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return nullptr; }
   if (f & (LIBXSMM_GEMM_FLAG_VNNI_B | LIBXSMM_GEMM_FLAG_VNNI_C)) { set_error(-3, "%s: VNNI layouts of B and C are not taken (A flat or VNNI-2, B and C flat)", fn); return nullptr; }
   if (ta && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) { set_error(-3, "%s: a VNNI-2 A is not taken together with TRANS_A (a transposed A is flat)", fn); return nullptr; }
-  const unsigned int allowed = LIBXSMM_GEMM_FLAG_BETA_0 | LIBXSMM_GEMM_FLAG_ALIGN_A | LIBXSMM_GEMM_FLAG_ALIGN_C_NTS_HINT | LIBXSMM_GEMM_FLAG_NO_RESET_TILECONFIG |
-    LIBXSMM_GEMM_FLAG_NO_SETUP_TILECONFIG | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_USE_XGEMM_ABI |
-    (offsets ? (unsigned int)(LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B) : (unsigned int)LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS) |
-    (ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
-  if (f & ~allowed) {
-    set_error(-3, offsets ? "%s: flags 0x%x are not taken (beta, VNNI_A, TRANS_A, TRANS_B and the hints only)" : "%s: flags 0x%x are not taken (beta, VNNI_A and the hints only)", fn, f & ~allowed);
+  if (shape == kGroupShapeFlags) {
+    set_error(-3, offsets ? "%s: flags 0x%x are not taken (beta, VNNI_A, TRANS_A, TRANS_B and the hints only)" : "%s: flags 0x%x are not taken (beta, VNNI_A and the hints only)", fn, f & ~(kGroupTileFlags | own));
     return nullptr;
   }
-  // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers): the grouped kernels' bound; a transposed operand spans lda x m / ldb x k
-  const unsigned long long lim = 1ull << 31;
-  if ((unsigned long long)d.lda * (ta ? d.m : d.k + 1) >= lim || (unsigned long long)d.ldb * (tb ? d.k : d.n) >= lim || (unsigned long long)d.ldc * d.n >= lim) {
-    set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return nullptr;
-  }
-  cls = f64 ? 2 : (bf16 ? 1 : 0);
-  const int tile = (f64 || (d.m <= 16 && d.n <= 16)) ? 16 : 32;
-  std::memset(&g, 0, sizeof(g));
-  g.m = (int)d.m; g.n = (int)d.n; g.k = (int)d.k; g.lda = (int)d.lda; g.ldb = (int)d.ldb; g.ldc = (int)d.ldc;
-  g.tile = tile; g.tiles_m = (int)((d.m + tile - 1) / tile); g.tiles_n = (int)((d.n + tile - 1) / tile);
-  g.beta1 = (f & LIBXSMM_GEMM_FLAG_BETA_0) ? 0 : 1;
-  g.vnni_a = (bf16 && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
-  g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
+  if (shape == kGroupShapeLd) { set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return nullptr; }
   // what the leading dimension allows of the wider loads; the block pointers are tested per product on the device
-  const unsigned long long esz = bf16 ? 2 : (f64 ? 8 : 4), colb = (unsigned long long)d.ldb * esz;
-  g.a_vec4 = bf16 ? 1 : 0; g.b_vec16 = (!tb && (colb & 15) == 0) ? 1 : 0; g.b_vec8 = (!tb && (colb & 7) == 0) ? 1 : 0;
+  const unsigned long long esz = cls == 1 ? 2 : (cls == 2 ? 8 : 4), colb = (unsigned long long)d.ldb * esz;
+  g.a_vec4 = cls == 1 ? 1 : 0; g.b_vec16 = (!tb && (colb & 15) == 0) ? 1 : 0; g.b_vec8 = (!tb && (colb & 7) == 0) ? 1 : 0;
   if (offsets) {
     const libxsmm_gemm_param* q = (const libxsmm_gemm_param*)param;
     g.a = (const char*)q->a.primary; g.b = (const char*)q->b.primary; g.c = (char*)q->c.primary;
@@ -2448,109 +2444,78 @@ static bool segments_operators(const char* fn, const libxsmm_gemm_descriptor& d,
   if (cls == 2 && (colbias || act != 0)) { set_error(-3, "%s: f64 ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
   return true;
 }
+// The one path behind the four entries.  `offsets`: the lists hold signed byte offsets from the bases in param [ref: gemm ref :509-513, :186-188] -- a
+// pattern's lists are computed once and serve every buffer the bases point at -- and the operands may be transposed, the backward passes of a block-sparse
+// layer.  `ext`: the handle's column bias, ReLU (+ bitmask) or sigmoid are applied per segment inside the launch, as the reference's fused call does
+// [ref: gemm ref :294-372]; the bias and mask blocks come from d_list / mask_list, or from param->d.primary / param->c.secondary plus their offsets (without
+// d_list the one bias is shared).  Nothing is staged, so every one of the four calls can be captured.
+static void run_segments(const char* fn, bool ext, bool offsets, const void* kernel, const void* param, size_t nsegments, const unsigned long long* seg_ptr,
+  const void* a_list, const void* b_list, const void* c_list, const void* d_list, const void* mask_list) {
+  if (nsegments == 0) return;
+  SegmentsLaunch l;
+  std::memset(&l, 0, sizeof(l));
+  unsigned long long tiles = 0;
+  KernelCtx* k = segments_validate(fn, ext, kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, l.g, l.cls, tiles, offsets ? &l.forms : nullptr);
+  if (!k) return;
+  GemmSegEpilogue e; GemmSegOffsEpilogue eo;
+  if (ext) {
+    const libxsmm_gemm_ext_param* p = (const libxsmm_gemm_ext_param*)param;
+    int colbias = 0, act = 0;
+    if (!segments_operators(fn, k->g, l.cls, colbias, act)) return;
+    const int mask_ld = ((int)k->g.ldc + 15) / 16 * 16;
+    if (offsets) {
+      std::memset(&eo, 0, sizeof(eo));
+      eo.colbias = colbias; eo.act = act; eo.a_wide = (l.forms >> 2) & 3;
+      if (colbias) {
+        eo.d = (const char*)p->d.primary; eo.d_offs = (const long long*)d_list;
+        if (!eo.d) { set_error(-2, "%s: fused column bias requested but param->d.primary (the base d_offs is added to; the shared bias without d_offs) is NULL", fn); return; }
+      }
+      if (act == 2) {
+        eo.mask = (char*)p->c.secondary; eo.mask_offs = (const long long*)mask_list; eo.mask_ld = mask_ld;
+        if (!mask_list) { set_error(-2, "%s: ReLU bitmask requested but mask_offs is NULL", fn); return; }
+        if (!eo.mask) { set_error(-2, "%s: ReLU bitmask requested but param->c.secondary (the base mask_offs is added to) is NULL", fn); return; }
+      }
+    } else {
+      std::memset(&e, 0, sizeof(e));
+      e.colbias = colbias; e.act = act;
+      if (colbias) {
+        e.d_list = (const void* const*)d_list; e.d = (const char*)p->d.primary;
+        if (!d_list && !e.d) { set_error(-2, "%s: fused column bias requested but d_list and param->d.primary are both NULL", fn); return; }
+      }
+      if (act == 2) {
+        e.mask_list = (void* const*)mask_list; e.mask_ld = mask_ld;
+        if (!mask_list) { set_error(-2, "%s: ReLU bitmask requested but mask_list is NULL", fn); return; }
+      }
+    }
+    // an ext handle without operators is the plain product: it runs the plain kernels (f64 among them)
+    l.fused = colbias != 0 || act != 0;
+    l.epilogue = offsets ? (const void*)&eo : (const void*)&e;
+  }
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  if (tiles == 0) return;                               // m or n is 0: no C
+  l.items = (unsigned long long)nsegments * tiles; l.seg_ptr = seg_ptr; l.a_list = a_list; l.b_list = b_list; l.c_list = c_list; l.offsets = offsets;
+  const char* kname = nullptr;
+  const int err = launch_gemm_segments(l, tls().stream, &kname);
+  k->kname_batched = kname;
+  finish_launch(err, kname);
+}
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
   const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list) {
-  static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments";
-  if (nsegments == 0) return;
-  GemmGroupDesc g; int cls = 0; unsigned long long tiles = 0;
-  KernelCtx* k = segments_validate(fn, false, (const void*)kernel, param, nsegments, seg_ptr, (const void*)a_list, (const void*)b_list, (const void*)c_list, g, cls, tiles);
-  if (!k) return;
-  coalesce_flush();
-  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
-  scratch_reset();
-  if (tiles == 0) return;                               // m or n is 0: no C
-  const char* kname = gemm_segments_kernel_name(cls);
-  const int err = launch_gemm_segments(g, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream);
-  k->kname_batched = kname;
-  finish_launch(err, kname);
+  run_segments("libxsmm_hip_gemm_batch_reduce_segments", false, false, (const void*)kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, nullptr, nullptr);
 }
-// The same call through an ext handle (libxsmm_dispatch_brgemm_ext): the column bias, the ReLU (+ bitmask) or the sigmoid of the handle are applied per
-// segment inside the launch, as the reference's fused call does [ref: gemm ref :294-372].  The operators are decoded as run_gemm decodes them; the bias and mask
-// blocks come from two more device-accessible lists (or one shared bias by value), so this call, too, stages nothing and can be captured.
 LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param, size_t nsegments,
   const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list, const void* const* d_list, void* const* mask_list) {
-  static const char* const fn = "libxsmm_hip_gemm_ext_batch_reduce_segments";
-  if (nsegments == 0) return;
-  GemmGroupDesc g; int cls = 0; unsigned long long tiles = 0;
-  KernelCtx* k = segments_validate(fn, true, (const void*)kernel, param, nsegments, seg_ptr, (const void*)a_list, (const void*)b_list, (const void*)c_list, g, cls, tiles);
-  if (!k) return;
-  const libxsmm_gemm_descriptor& d = k->g;
-  GemmSegEpilogue e;
-  std::memset(&e, 0, sizeof(e));
-  if (!segments_operators(fn, d, cls, e.colbias, e.act)) return;
-  const bool fused = e.colbias != 0 || e.act != 0;
-  if (e.colbias) {
-    e.d_list = d_list; e.d = (const char*)param->d.primary;
-    if (!d_list && !e.d) { set_error(-2, "%s: fused column bias requested but d_list and param->d.primary are both NULL", fn); return; }
-  }
-  if (e.act == 2) {
-    e.mask_list = mask_list; e.mask_ld = ((int)d.ldc + 15) / 16 * 16;
-    if (!mask_list) { set_error(-2, "%s: ReLU bitmask requested but mask_list is NULL", fn); return; }
-  }
-  coalesce_flush();
-  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
-  scratch_reset();
-  if (tiles == 0) return;                               // m or n is 0: no C
-  // an ext handle without operators is the plain product: it runs the plain kernels (f64 among them)
-  const char* kname = fused ? gemm_segments_fused_kernel_name(cls) : gemm_segments_kernel_name(cls);
-  const int err = fused ? launch_gemm_segments_fused(g, e, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream)
-                        : launch_gemm_segments(g, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_list, b_list, c_list, tls().stream);
-  k->kname_batched = kname;
-  finish_launch(err, kname);
+  run_segments("libxsmm_hip_gemm_ext_batch_reduce_segments", true, false, (const void*)kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, d_list, mask_list);
 }
-// Segments through OFFSET batch-reduce handles [ref: gemm ref :509-513, :186-188]: three bases by value, signed byte offsets in the lists -- a pattern's lists are
-// computed once and serve every buffer the bases point at -- and transposed operands, the backward passes of a block-sparse layer (gemm_segments_kernels.hip).
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
   const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs) {
-  static const char* const fn = "libxsmm_hip_gemm_batch_reduce_segments_offsets";
-  if (nsegments == 0) return;
-  GemmGroupDesc g; int cls = 0, forms = 0; unsigned long long tiles = 0;
-  KernelCtx* k = segments_validate(fn, false, (const void*)kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, g, cls, tiles, &forms);
-  if (!k) return;
-  coalesce_flush();
-  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
-  scratch_reset();
-  if (tiles == 0) return;                               // m or n is 0: no C
-  const char* kname = gemm_segments_offs_kernel_name(cls, forms);
-  const int err = launch_gemm_segments_offs(g, forms, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_offs, b_offs, c_offs, tls().stream);
-  k->kname_batched = kname;
-  finish_launch(err, kname);
+  run_segments("libxsmm_hip_gemm_batch_reduce_segments_offsets", false, true, (const void*)kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, nullptr, nullptr);
 }
-// The fourth corner: OFFSET segments through an ext handle [ref: gemm ref :294-372, :509-513].  Five bases by value -- A, B, C, the bias base (d.primary) and
-// the mask base (c.secondary) -- and two more offset lists; the operators are those of libxsmm_hip_gemm_ext_batch_reduce_segments, decoded in one place
-// (segments_operators).  Nothing is staged, so this call, too, can be captured (gemm_segments_offs_fused_kernels.hip).
 LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param, size_t nsegments,
   const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs, const long long* d_offs, const long long* mask_offs) {
-  static const char* const fn = "libxsmm_hip_gemm_ext_batch_reduce_segments_offsets";
-  if (nsegments == 0) return;
-  GemmGroupDesc g; int cls = 0, forms = 0; unsigned long long tiles = 0;
-  KernelCtx* k = segments_validate(fn, true, (const void*)kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, g, cls, tiles, &forms);
-  if (!k) return;
-  const libxsmm_gemm_descriptor& d = k->g;
-  GemmSegOffsEpilogue e;
-  std::memset(&e, 0, sizeof(e));
-  if (!segments_operators(fn, d, cls, e.colbias, e.act)) return;
-  const bool fused = e.colbias != 0 || e.act != 0;
-  if (e.colbias) {
-    e.d = (const char*)param->d.primary; e.d_offs = d_offs;
-    if (!e.d) { set_error(-2, "%s: fused column bias requested but param->d.primary (the base d_offs is added to; the shared bias without d_offs) is NULL", fn); return; }
-  }
-  if (e.act == 2) {
-    e.mask = (char*)param->c.secondary; e.mask_offs = mask_offs; e.mask_ld = ((int)d.ldc + 15) / 16 * 16;
-    if (!mask_offs) { set_error(-2, "%s: ReLU bitmask requested but mask_offs is NULL", fn); return; }
-    if (!e.mask) { set_error(-2, "%s: ReLU bitmask requested but param->c.secondary (the base mask_offs is added to) is NULL", fn); return; }
-  }
-  e.a_wide = (forms >> 2) & 3;
-  coalesce_flush();
-  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
-  scratch_reset();
-  if (tiles == 0) return;                               // m or n is 0: no C
-  // an ext handle without operators is the plain product: it runs the plain offsets kernels (f64 among them)
-  const char* kname = fused ? gemm_segments_offs_fused_kernel_name(cls, forms) : gemm_segments_offs_kernel_name(cls, forms);
-  const int err = fused ? launch_gemm_segments_offs_fused(g, e, forms, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_offs, b_offs, c_offs, tls().stream)
-                        : launch_gemm_segments_offs(g, forms, cls, (unsigned long long)nsegments * tiles, seg_ptr, a_offs, b_offs, c_offs, tls().stream);
-  k->kname_batched = kname;
-  finish_launch(err, kname);
+  run_segments("libxsmm_hip_gemm_ext_batch_reduce_segments_offsets", true, true, (const void*)kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, d_offs, mask_offs);
 }
 // ---- multi-device launch from ONE host thread (the reference's scale-out axis is the caller's loop,
 // samples/xgemm/gemm_kernel.c:4063-4066) --------------------------------------------------------------------------------------------------------

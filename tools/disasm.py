@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Disassembly of one gfx950 kernel compiled into libxsmm_amd.so (no GPU needed):  python tools/disasm.py <mangled-name-substring> [out.s]"""
+"""Disassembly of one gfx950 kernel compiled into libxsmm_amd.so (no GPU needed):  python tools/disasm.py <mangled-name-substring> [out.s] [--lib path/to/libxsmm_amd.so]
+(--lib: a variant build next to the shipped one, to compare a kernel's instructions before and after a change)"""
 import os
 import subprocess
 import sys
@@ -10,8 +11,12 @@ from kernel_resources import LLVM, ROOT, code_objects  # noqa: E402
 
 
 def main():
-    want = sys.argv[1]
     lib = os.path.join(ROOT, "libxsmm_amd", "lib", "libxsmm_amd.so")
+    if "--lib" in sys.argv:
+        at = sys.argv.index("--lib")
+        lib = sys.argv[at + 1]
+        del sys.argv[at:at + 2]
+    want = sys.argv[1]
     for image in code_objects(lib):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(image); f.flush()
