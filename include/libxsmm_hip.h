@@ -218,6 +218,63 @@ typedef struct libxsmm_hip_gemm_group {
 } libxsmm_hip_gemm_group;
 LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* groups, size_t ngroups);
 /**
+ * Grouped batch through ext handles: a layer of several GEMM shapes, each followed by its bias and activation -- the reference's fused BRGEMM call
+ * [ref: src/generator_gemm_reference_impl.c:294-372] issued from the caller's loop over shapes [ref: samples/xgemm/gemm_kernel.c:4063-4066]:
+ *   libxsmm_hip_gemm_ext_batch_grouped(groups, ngroups)
+ *     ==  for (g = 0; g < ngroups; ++g)
+ *           libxsmm_hip_gemm_ext_batch_strided(groups[g].kernel, &groups[g].param, groups[g].count, groups[g].stride_a, groups[g].stride_b,
+ *                                              groups[g].stride_c, groups[g].stride_d, groups[g].stride_mask);
+ * The contract is that of libxsmm_hip_gemm_batch_grouped: the caller declares the groups independent, operands are device-accessible, every group is
+ * validated before anything is launched, and the call follows the thread's launch mode (blocking, stream-ordered, coalescing -- flushed first --, pipeline
+ * section).  Groups through ext handles of f32 x f32 -> f32 or bf16 x bf16 -> f32 / bf16 (plain or STRIDE batch-reduce, A flat or VNNI_A, B flat, C not VNNI,
+ * NN, beta 0 or 1, the hints) with BINARY_ADD + BCAST_COL_IN_0/1, cp RELU (with or without BITMASK_2BYTEMULT) or cp SIGMOID leave as ONE launch per fused
+ * precision class; ext handles without operators join the plain classes of libxsmm_hip_gemm_batch_grouped under its rule.  A fused f32 group of 2048 work
+ * items (element x C tile) or more on 32 x 32 tiles (m or n above 16) whose m and n are multiples of 16 is faster on its own ext kernel and leaves, every other fused f32 group
+ * stays (measured: DESIGN.md section 8.1); a class with a single group runs that group's own kernel.  Everything else libxsmm_hip_gemm_ext_batch_strided accepts (other
+ * types, transposes, ADDRESS / OFFSET batch-reduce, a batch-reduce count of 0, 2^32 items or more) runs as that group's own ext strided launch, in list
+ * order on the same stream, bit for bit what that call computes.
+ * Per element of a fused group (the semantics of libxsmm_hip_gemm_ext_batch_reduce_segments for one C block): the bias has C's type; the accumulator starts
+ * at bias[i], at bias[i] + C(i,j) (beta = 1, one f32 add), or at C(i,j) / +0 without a bias; one chain over (block, k); mask bit i % 8 of byte
+ * i / 8 + j * (mask_ld / 8), mask_ld = ldc rounded up to 16, is !(x <= 0) of the sum and is written for i < m, j < n only; then the activation; then one
+ * rounding for a bf16 C.  For f32 the result is the k-ordered fmaf chain started at the bias, bit for bit.
+ * Error -2: groups == NULL with ngroups > 0, a batch-reduce handle without op.tertiary, a column-bias handle with param.d.primary NULL, a bitmask handle
+ * with param.c.secondary NULL; -3: an unknown handle, a non-ext / TPP / equation / sparse handle (plain handles go to libxsmm_hip_gemm_batch_grouped), or a
+ * call while the thread's stream is being captured (the tables live for the call only: make the list a plan, below); -4: no device.  count = 0 skips a
+ * group; ngroups = 0 does nothing.
+ */
+typedef struct libxsmm_hip_gemm_ext_group {
+  libxsmm_gemmfunction_ext kernel;  /* any handle libxsmm_hip_gemm_ext_batch_strided accepts */
+  libxsmm_gemm_ext_param   param;   /* element 0; d.primary = bias, c.secondary = ReLU bitmask, op.tertiary = batch-reduce count */
+  size_t                   count;   /* elements of this group; 0 = skipped */
+  long long                stride_a, stride_b, stride_c, stride_d, stride_mask;   /* byte strides; 0 = shared */
+} libxsmm_hip_gemm_ext_group;
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_grouped(const libxsmm_hip_gemm_ext_group* groups, size_t ngroups);
+/**
+ * Group plans: the group tables of a list built once and kept in device memory that the plan owns -- for the caller whose list is fixed (10 000 groups of
+ * one problem: no validation, no table build and no upload per call) and for graph capture, which the two grouped calls refuse.
+ *   plan = libxsmm_hip_gemm_group_plan_create(groups, ngroups)         (a list of libxsmm_hip_gemm_batch_grouped)
+ *   plan = libxsmm_hip_gemm_ext_group_plan_create(groups, ngroups)     (a list of libxsmm_hip_gemm_ext_batch_grouped)
+ *   libxsmm_hip_gemm_group_plan_launch(plan)    ==  the grouped call on the list given at create
+ * Create validates with the codes of the call and applies its launch rule; the caller's arrays (the list, and the batch-reduce counts op.tertiary points
+ * at: their VALUES are kept) may be freed afterwards.  A plan takes only groups of the kind that can enter the grouped kernels (the eligible handles
+ * above); those that the launch rule sends to their own kernels (large f32 groups, a class with one group) run their own strided launch from a stored copy
+ * of their param.  Any other group -- other types, transposes, ADDRESS / OFFSET batch-reduce, packed sparse, a count of 0 batch-reduce blocks -- is refused:
+ * -3, NULL, the message names the group (such a launch may stage per-call host data, which a replayed graph cannot redo).  Create returns NULL with -4 when
+ * there is no device, after validation.  A plan belongs to the device that is current at create.
+ * Launch issues only kernel launches that read the resident tables, so it may be called while the thread's stream is being captured into a graph (in
+ * stream-ordered mode, like every captured call).  The operand bases travel in the tables: a replay computes from what the operands hold then.  It follows
+ * the thread's launch mode like the grouped calls.  -2: plan == NULL; -3: another device is current, or libxsmm_finalize released the plan's handles.
+ * libxsmm_hip_gemm_group_plan_launches(plan): the kernel launches one launch issues (libxsmm_hip_launch_count).
+ * Destroy waits for the thread's stream and frees the tables: a graph that captured a launch of the plan must not be replayed afterwards.  While the
+ * thread's stream is being captured it is refused (-3) and the plan is kept.
+ */
+typedef struct libxsmm_hip_gemm_group_plan libxsmm_hip_gemm_group_plan;
+LIBXSMM_API libxsmm_hip_gemm_group_plan* libxsmm_hip_gemm_group_plan_create(const libxsmm_hip_gemm_group* groups, size_t ngroups);
+LIBXSMM_API libxsmm_hip_gemm_group_plan* libxsmm_hip_gemm_ext_group_plan_create(const libxsmm_hip_gemm_ext_group* groups, size_t ngroups);
+LIBXSMM_API void libxsmm_hip_gemm_group_plan_launch(const libxsmm_hip_gemm_group_plan* plan);
+LIBXSMM_API int libxsmm_hip_gemm_group_plan_launches(const libxsmm_hip_gemm_group_plan* plan);
+LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan* plan);
+/**
  * Segments: a batch of ADDRESS batch-reduce calls whose reduce count differs from call to call -- the count is the one argument the reference re-reads on
  * every call [ref: src/generator_gemm_reference_impl.c:490-492] -- as ONE launch: a block-sparse matrix times a dense one (one BRGEMM per block row of C),
  * a stack of small products accumulating into blocks of C, a convolution whose border pixels see fewer taps.  `kernel` is an ADDRESS batch-reduce handle

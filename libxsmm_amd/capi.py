@@ -168,6 +168,11 @@ class GemmGroup(C.Structure):          # libxsmm_hip_gemm_group (include/libxsmm
                 ("stride_a", C.c_longlong), ("stride_b", C.c_longlong), ("stride_c", C.c_longlong)]
 
 
+class GemmExtGroup(C.Structure):       # libxsmm_hip_gemm_ext_group (include/libxsmm_hip.h): one strided batch of an ext grouped call
+    _fields_ = [("kernel", C.c_void_p), ("param", GemmExtParam), ("count", C.c_size_t),
+                ("stride_a", C.c_longlong), ("stride_b", C.c_longlong), ("stride_c", C.c_longlong), ("stride_d", C.c_longlong), ("stride_mask", C.c_longlong)]
+
+
 class KernelInfo(C.Structure):
     _fields_ = [("kind", C.c_int), ("nflops", C.c_uint), ("code_size", C.c_size_t), ("is_reference_kernel", C.c_uint)]
 
@@ -289,6 +294,12 @@ class Api:
             self.hip_gemm_ext_batch_strided_2d = f("hip_gemm_ext_batch_strided_2d", None, [vp, C.POINTER(GemmExtParam), C.c_size_t, C.c_size_t, ll, ll, ll, ll, ll, ll, ll])
             self.hip_gemm_batch_pointers = f("hip_gemm_batch_pointers", None, [vp, C.POINTER(GemmParam), C.c_size_t, vp, vp, vp])
             self.hip_gemm_batch_grouped = f("hip_gemm_batch_grouped", None, [C.POINTER(GemmGroup), C.c_size_t])
+            self.hip_gemm_ext_batch_grouped = f("hip_gemm_ext_batch_grouped", None, [C.POINTER(GemmExtGroup), C.c_size_t])
+            self.hip_gemm_group_plan_create = f("hip_gemm_group_plan_create", vp, [C.POINTER(GemmGroup), C.c_size_t])
+            self.hip_gemm_ext_group_plan_create = f("hip_gemm_ext_group_plan_create", vp, [C.POINTER(GemmExtGroup), C.c_size_t])
+            self.hip_gemm_group_plan_launch = f("hip_gemm_group_plan_launch", None, [vp])
+            self.hip_gemm_group_plan_launches = f("hip_gemm_group_plan_launches", C.c_int, [vp])
+            self.hip_gemm_group_plan_destroy = f("hip_gemm_group_plan_destroy", None, [vp])
             self.hip_gemm_batch_reduce_segments = f("hip_gemm_batch_reduce_segments", None, [vp, C.POINTER(GemmParam), C.c_size_t, vp, vp, vp, vp])
             self.hip_gemm_ext_batch_reduce_segments = f("hip_gemm_ext_batch_reduce_segments", None, [vp, C.POINTER(GemmExtParam), C.c_size_t, vp, vp, vp, vp, vp, vp])
             self.hip_gemm_batch_reduce_segments_offsets = f("hip_gemm_batch_reduce_segments_offsets", None, [vp, C.POINTER(GemmParam), C.c_size_t, vp, vp, vp, vp])

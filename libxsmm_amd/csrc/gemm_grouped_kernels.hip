@@ -9,17 +9,25 @@
 // ragged k) are gemm_group_tile.hpp, shared with the segment kernels; here a tile walks a STRIDE batch-reduce chain (one block for plain GEMM handles).
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <type_traits>
 #include "internal.hpp"
 #include "gemm_device.hpp"
 #include "bf16_cvt.hpp"
 #include "gemm_group_tile.hpp"
+#include "gemm_grouped.hpp"
 
 namespace xamd {
 
 using namespace group_tile;
 
-template <bool BF16, typename Table>
-__device__ __forceinline__ void grouped_body(const Table& groups, int ngroups, unsigned long long total) {
+// EpiTable: the parallel table of the fused launches (GemmGroupEpi, gemm_grouped.hpp: libxsmm_hip_gemm_ext_batch_grouped, the group plans); NoEpiTable: the
+// plain kernels, whose instances are what they were before the parameter existed (every use of the table sits behind `if constexpr`).
+struct NoEpiTable {};
+template <typename T> struct is_no_epi { static constexpr bool value = false; };
+template <> struct is_no_epi<NoEpiTable> { static constexpr bool value = true; };
+
+template <bool BF16, typename Table, typename EpiTable = NoEpiTable>
+__device__ __forceinline__ void grouped_body(const Table& groups, int ngroups, unsigned long long total, const EpiTable& epis = EpiTable()) {
   const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const unsigned int lane = threadIdx.x & 63u;
   const unsigned long long step = (unsigned long long)gridDim.x * 4u;
@@ -38,10 +46,24 @@ __device__ __forceinline__ void grouped_body(const Table& groups, int ngroups, u
     gcptr b = (gcptr)g.b + (long long)e * g.sb;
     gptr c = (gptr)g.c + (long long)e * g.sc;
     const StrideChain ch = stride_chain(g, a, b);
-    if (g.tile == 32) {
-      if constexpr (BF16) tile_bf16<32, false>(g, ch, c, (int)tm * 32, (int)tn * 32, lane); else tile_f32<32, false>(g, ch, c, (int)tm * 32, (int)tn * 32, lane);
-    } else {
-      if constexpr (BF16) tile_bf16<16, false>(g, ch, c, (int)tm * 16, (int)tn * 16, lane); else tile_f32<16, false>(g, ch, c, (int)tm * 16, (int)tn * 16, lane);
+    // one tile call for both forms: the plain kernels pass NoEpilogue (their instances are what they were), the fused ones the element's epilogue
+    const auto run_tile = [&](const auto& ep) {
+      typedef typename std::remove_cv<typename std::remove_reference<decltype(ep)>::type>::type Epi;
+      if (g.tile == 32) {
+        if constexpr (BF16) tile_bf16<32, false, StrideChain, Epi>(g, ch, c, (int)tm * 32, (int)tn * 32, lane, ep); else tile_f32<32, false, StrideChain, Epi>(g, ch, c, (int)tm * 32, (int)tn * 32, lane, ep);
+      } else {
+        if constexpr (BF16) tile_bf16<16, false, StrideChain, Epi>(g, ch, c, (int)tm * 16, (int)tn * 16, lane, ep); else tile_f32<16, false, StrideChain, Epi>(g, ch, c, (int)tm * 16, (int)tn * 16, lane, ep);
+      }
+    };
+    if constexpr (is_no_epi<EpiTable>::value) run_tile(NoEpilogue());
+    else {
+      // bias and mask block of element e of the group -- the group and the element are the wave's, so every member is wave-uniform
+      const GemmGroupEpi ge = epis[lo];
+      FusedEpilogue ep;
+      ep.d = (gcptr)ge.d + (long long)e * ge.sd;
+      ep.mask = (GM unsigned char*)ge.mask + (long long)e * ge.smask;
+      ep.colbias = ge.colbias; ep.act = ge.act; ep.mask_ld = ge.mask_ld;
+      run_tile(ep);
     }
   }
 }
@@ -54,6 +76,42 @@ __global__ __launch_bounds__(256) void gemm_grouped_f32_kernel(const GemmGroupDe
 __global__ __launch_bounds__(256) void gemm_grouped_bf16_kernel(const GemmGroupDesc* __restrict__ groups, int ngroups, unsigned long long total) { grouped_body<true>(groups, ngroups, total); }
 __global__ __launch_bounds__(256) void gemm_grouped_f32_inline_kernel(GroupedInline tab, int ngroups, unsigned long long total) { grouped_body<false>(tab.g, ngroups, total); }
 __global__ __launch_bounds__(256) void gemm_grouped_bf16_inline_kernel(GroupedInline tab, int ngroups, unsigned long long total) { grouped_body<true>(tab.g, ngroups, total); }
+
+// The fused forms: the same body with FusedEpilogue tiles; the epilogue entries ride next to the group entries, in the arguments (kGroupedFusedInline groups)
+// or behind a second pointer.
+struct GroupedFusedInline { GemmGroupDesc g[kGroupedFusedInline]; GemmGroupEpi e[kGroupedFusedInline]; };
+static_assert(sizeof(GroupedFusedInline) + 16 + 256 <= 4096, "the inline fused table, ngroups, total and the hidden arguments must fit the 4 KiB kernel argument segment");
+__global__ __launch_bounds__(256) void gemm_grouped_f32_fused_kernel(const GemmGroupDesc* __restrict__ groups, const GemmGroupEpi* __restrict__ epis, int ngroups, unsigned long long total) {
+  grouped_body<false>(groups, ngroups, total, epis);
+}
+__global__ __launch_bounds__(256) void gemm_grouped_bf16_fused_kernel(const GemmGroupDesc* __restrict__ groups, const GemmGroupEpi* __restrict__ epis, int ngroups, unsigned long long total) {
+  grouped_body<true>(groups, ngroups, total, epis);
+}
+__global__ __launch_bounds__(256) void gemm_grouped_f32_fused_inline_kernel(GroupedFusedInline tab, int ngroups, unsigned long long total) { grouped_body<false>(tab.g, ngroups, total, tab.e); }
+__global__ __launch_bounds__(256) void gemm_grouped_bf16_fused_inline_kernel(GroupedFusedInline tab, int ngroups, unsigned long long total) { grouped_body<true>(tab.g, ngroups, total, tab.e); }
+
+const char* gemm_grouped_fused_kernel_name(int bf16) { return bf16 ? "gemm_grouped_bf16_fused_kernel" : "gemm_grouped_f32_fused_kernel"; }
+int launch_gemm_grouped_fused(const GemmGroupDesc* table, const GemmGroupEpi* epi, int ngroups, unsigned long long items, int bf16, void* stream) {
+  if (ngroups <= 0 || items == 0) return 0;
+  const unsigned int grid = group_grid(items);
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, table, epi, ngroups, items);
+  else hipLaunchKernelGGL(gemm_grouped_f32_fused_kernel, dim3(grid), dim3(256), 0, st, table, epi, ngroups, items);
+  return (int)hipGetLastError();
+}
+int launch_gemm_grouped_fused_inline(const GemmGroupDesc* host_table, const GemmGroupEpi* host_epi, int ngroups, unsigned long long items, int bf16, void* stream) {
+  if (ngroups <= 0 || items == 0) return 0;
+  if (ngroups > kGroupedFusedInline) return (int)hipErrorInvalidValue;
+  GroupedFusedInline tab;
+  std::memset(&tab, 0, sizeof(tab));
+  std::memcpy(tab.g, host_table, (size_t)ngroups * sizeof(GemmGroupDesc));
+  std::memcpy(tab.e, host_epi, (size_t)ngroups * sizeof(GemmGroupEpi));
+  const unsigned int grid = group_grid(items);
+  hipStream_t st = (hipStream_t)stream;
+  if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_fused_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);
+  else hipLaunchKernelGGL(gemm_grouped_f32_fused_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);
+  return (int)hipGetLastError();
+}
 
 const char* gemm_grouped_kernel_name(int bf16) { return bf16 ? "gemm_grouped_bf16_kernel" : "gemm_grouped_f32_kernel"; }
 

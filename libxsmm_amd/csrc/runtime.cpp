@@ -7,6 +7,7 @@
 // and says why (stderr, once) -- the library fails loudly instead of silently computing on the host.
 #include <hip/hip_runtime_api.h>
 #include "internal.hpp"
+#include "gemm_grouped.hpp"
 
 #include <sys/mman.h>
 #include <unistd.h>
@@ -2251,6 +2252,17 @@ LIBXSMM_API void libxsmm_hip_meqn_batch_strided_accumulate(libxsmm_meqn_function
   scratch_reset();
   if (const char* kname = run_meqn_acc(c->eqn, param, b, carried)) c->kname_batched = kname;
 }
+// The operators of an ext handle as the FusedEpilogue tiles take them (gemm_group_tile.hpp), decoded as run_gemm decodes them: colbias, and act 0 none, 1 ReLU,
+// 2 ReLU + bitmask, 3 sigmoid.  false for every other operator; no error is set (segments: an error; grouped: the group runs on its own).
+static bool fused_operators(const libxsmm_gemm_descriptor& d, int& colbias_out, int& act) {
+  const bool colbias = d.bin_type == LIBXSMM_MELTW_TYPE_BINARY_ADD && (d.bin_flags & (LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_0 | LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_1));
+  if ((d.bin_type != LIBXSMM_MELTW_TYPE_BINARY_NONE && !colbias) || d.ap_type != 0 || d.bp_type != 0 ||
+      (d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_NONE && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_RELU && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_SIGMOID)) return false;
+  colbias_out = colbias ? 1 : 0; act = 0;
+  if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_RELU) act = (d.cp_flags & LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT) ? 2 : 1;
+  else if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_SIGMOID) act = 3;
+  return true;
+}
 // ---- grouped batches (libxsmm_hip_gemm_batch_grouped): several shapes, one launch per precision class --------------------------------------------------
 // A group enters the grouped kernels (gemm_grouped_kernels.hip) when its handle is a plain GEMM or a STRIDE batch-reduce handle of f32 x f32 -> f32 or
 // bf16 x bf16 -> f32 / bf16 (A flat or VNNI-2, B flat, C not VNNI), NN, with no flag beyond beta and the hints; `cls` = 0 (f32) or 1 (bf16).
@@ -2282,11 +2294,12 @@ static GroupShape group_shape(const libxsmm_gemm_descriptor& d, unsigned int f, 
   g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
   return kGroupShapeOk;
 }
-static bool grouped_eligible(const KernelCtx* k, const libxsmm_hip_gemm_group& grp, GemmGroupDesc& g, int& cls) {
+// (`abi`: LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI for the entries that take ext handles)
+static bool grouped_eligible(const KernelCtx* k, const libxsmm_hip_gemm_group& grp, GemmGroupDesc& g, int& cls, unsigned int abi = 0) {
   if (k->kind != K_GEMM) return false;
   const libxsmm_gemm_descriptor& d = k->g;
   const unsigned int f = effective_gemm_flags(d);
-  if (group_shape(d, f, LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE, g, cls) != kGroupShapeOk || cls == 2) return false;
+  if (group_shape(d, f, LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE | abi, g, cls) != kGroupShapeOk || cls == 2) return false;
   const libxsmm_gemm_param& p = grp.param;
   if (d.m == 0 || d.n == 0 || d.k == 0 || !p.a.primary || !p.b.primary || !p.c.primary) return false;
   unsigned long long brc = 1;
@@ -2337,6 +2350,7 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* gr
   for (size_t i = 0; i < ngroups; ++i) {
     if (groups[i].count == 0) continue;
     GemmGroupDesc gd; int cls = 0;
+    // (grouped_build, further down, holds a copy of this rule and of the single-group rule below for the group plans: change both together)
     // measured: an f32 group of 2048 work items or more runs at least as fast on its own tuned kernel (p16s, lean, wg64, ragged families:
     // 1.0 - 2x the grouped kernel's rate at 1024 - 4096 problems) as inside the grouped launch, so it leaves it (gd.first: the group's item count); bf16 groups
     // gain from the merge and stay
@@ -2365,6 +2379,256 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* gr
     BatchSpec b; b.count = grp.count; b.s[0] = grp.stride_a; b.s[1] = grp.stride_b; b.s[2] = grp.stride_c;
     if (c->kind == K_GEMM) run_gemm(c, &grp.param, b); else run_spmm(c, &grp.param, b);
   }
+}
+// ---- fused grouped batches (libxsmm_hip_gemm_ext_batch_grouped) and group plans (libxsmm_hip_gemm_group_plan_*) ----------------------------------------
+// One list format behind three users: the ext entry, and the plans made from a plain or an ext list.  A group that enters the grouped kernels joins one of
+// four classes -- plain f32, plain bf16 (the kernels of libxsmm_hip_gemm_batch_grouped), fused f32, fused bf16 (FusedEpilogue tiles, with a GemmGroupEpi entry
+// next to its GemmGroupDesc) -- and every class leaves as one launch; every other group runs as its own strided launch from a copy of its param.
+// Measured: a fused f32 group of the plain rule's item count or more is faster on its own ext kernel only on 32-tiles with m and n
+// multiples of 16 (32^3, 48^3, 64^3: 1.2 - 1.5x); the other shapes (13^3, 16^3, 23^3, 40^3, 24 x 48 x 32) run as fast or faster inside the grouped launch and stay.
+static constexpr unsigned long long kGroupedOwnF32FusedItems = 2048;
+namespace {
+struct GroupIn { const void* kernel; const void* param; size_t param_bytes; size_t count; long long s[5]; };
+static GroupIn group_in(const libxsmm_hip_gemm_group& g) { return GroupIn{(const void*)g.kernel, &g.param, sizeof(g.param), g.count, {g.stride_a, g.stride_b, g.stride_c, 0, 0}}; }
+static GroupIn group_in(const libxsmm_hip_gemm_ext_group& g) {
+  return GroupIn{(const void*)g.kernel, &g.param, sizeof(g.param), g.count, {g.stride_a, g.stride_b, g.stride_c, g.stride_d, g.stride_mask}};
+}
+struct GroupedOwn {                                  // a group that runs as its own strided launch: everything the launch reads on the host, by value
+  size_t index; KernelCtx* k; libxsmm_gemm_ext_param param; unsigned long long brc; bool has_brc; BatchSpec b;
+};
+struct GroupedClass { std::vector<GemmGroupDesc> table; std::vector<GemmGroupEpi> epi; std::vector<size_t> member; unsigned long long items = 0; };
+struct GroupedBuild { GroupedClass cls[4]; std::vector<GroupedOwn> own; };       // cls: 0 f32, 1 bf16, 2 fused f32, 3 fused bf16
+constexpr unsigned int kBrFlags = LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE;
+
+// Every group is validated before anything is launched or built.  `ext`: the list holds libxsmm_hip_gemm_ext_group entries (ext handles and only those);
+// else the codes of libxsmm_hip_gemm_batch_grouped.  *any: a group with count > 0 exists.
+static bool grouped_validate(const char* fn, bool ext, const GroupIn* in, size_t ngroups, bool* any) {
+  *any = false;
+  for (size_t i = 0; i < ngroups; ++i) {
+    KernelCtx* c = ctx_from_handle(in[i].kernel);
+    if (!c) { set_error(-3, "%s: group %zu has an unknown kernel handle", fn, i); return false; }
+    if (in[i].count == 0) continue;
+    const bool is_ext = c->kind == K_GEMM && (c->g.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI);
+    if (ext) {
+      if (c->kind != K_GEMM) { set_error(-3, "%s: group %zu: handle is not a BRGEMM kernel (TPP, equation and sparse handles are not taken)", fn, i); return false; }
+      if (!is_ext) { set_error(-3, "%s: group %zu: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_grouped)", fn, i); return false; }
+    } else {
+      if (c->kind != K_GEMM && c->kind != K_SPMM_ASPARSE && c->kind != K_SPMM_BSPARSE) { set_error(-3, "%s: group %zu: handle is not a (BR)GEMM or packed sparse kernel", fn, i); return false; }
+      if (is_ext) { set_error(-3, "%s: group %zu: ext handles are not taken (use the ext form of this call)", fn, i); return false; }
+    }
+    const libxsmm_gemm_param* p = (const libxsmm_gemm_param*)in[i].param;           // {op, a, b, c} is the common prefix of both param structs
+    if (c->kind == K_GEMM && (c->g.flags & kBrFlags) && !p->op.tertiary) { set_error(-2, "%s: group %zu: BRGEMM handle without op.tertiary (batch-reduce count)", fn, i); return false; }
+    if (ext) {
+      const libxsmm_gemm_descriptor& d = c->g;
+      const libxsmm_gemm_ext_param* pe = (const libxsmm_gemm_ext_param*)in[i].param;
+      if (d.bin_type == LIBXSMM_MELTW_TYPE_BINARY_ADD && (d.bin_flags & (LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_0 | LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_1)) && !pe->d.primary) {
+        set_error(-2, "%s: group %zu: fused column bias requested but param.d.primary is NULL", fn, i); return false;
+      }
+      if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_RELU && (d.cp_flags & LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT) && !pe->c.secondary) {
+        set_error(-2, "%s: group %zu: ReLU bitmask requested but param.c.secondary is NULL", fn, i); return false;
+      }
+    }
+    *any = true;
+  }
+  return true;
+}
+static bool stream_is_capturing() {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (cur_stream() != nullptr && hipStreamIsCapturing(cur_stream(), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+  return cs != hipStreamCaptureStatusNone;
+}
+// The launch rule over a validated list: classes, the groups that leave them, and the exclusive item prefix of every class table.  `plan_fn` != NULL: a
+// group that cannot enter the grouped kernels at all is refused (-3; false) -- its own launch may stage per-call host data, which a replayed plan cannot redo.
+static bool grouped_build(const GroupIn* in, size_t ngroups, GroupedBuild& out, const char* plan_fn) {
+  std::vector<size_t> own;
+  for (size_t i = 0; i < ngroups; ++i) {
+    if (in[i].count == 0) continue;
+    KernelCtx* k = ctx_from_handle(in[i].kernel);
+    libxsmm_hip_gemm_group tg;
+    std::memset(&tg, 0, sizeof(tg));
+    std::memcpy(&tg.param, in[i].param, sizeof(tg.param));
+    tg.count = in[i].count; tg.stride_a = in[i].s[0]; tg.stride_b = in[i].s[1]; tg.stride_c = in[i].s[2];
+    GemmGroupDesc gd; int cls = 0, colbias = 0, act = 0;
+    const bool is_ext = k->kind == K_GEMM && (k->g.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI);
+    bool eligible = grouped_eligible(k, tg, gd, cls, is_ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
+    if (eligible && is_ext) eligible = fused_operators(k->g, colbias, act);
+    if (!eligible) {
+      if (plan_fn) {
+        set_error(-3, "%s: group %zu cannot enter the grouped kernels (f32 or bf16, NN, plain or STRIDE batch-reduce with a count above 0, bias / ReLU / sigmoid only): a plan does not take it", plan_fn, i);
+        return false;
+      }
+      own.push_back(i); continue;
+    }
+    const int c4 = cls + ((colbias || act) ? 2 : 0);
+    // the plain rule (libxsmm_hip_gemm_batch_grouped) and, for fused f32 groups, its measured counterpart: large f32 groups (fused: on 32-tiles with m and n multiples of 16) are faster on their own kernels
+    // (THE PLAIN HALF IS A COPY of the rule in libxsmm_hip_gemm_batch_grouped, which stays as it is: a plain plan equals that call only while the two agree)
+    const bool mn16 = gd.tile == 32 && gd.m % 16 == 0 && gd.n % 16 == 0;
+    if ((c4 == 0 && gd.first >= kGroupedOwnF32Items) || (c4 == 2 && gd.first >= kGroupedOwnF32FusedItems && mn16)) { own.push_back(i); continue; }
+    GroupedClass& gc = out.cls[c4];
+    gc.table.push_back(gd); gc.member.push_back(i);
+    if (c4 >= 2) {
+      const libxsmm_gemm_ext_param* pe = (const libxsmm_gemm_ext_param*)in[i].param;
+      GemmGroupEpi e;
+      std::memset(&e, 0, sizeof(e));
+      e.colbias = colbias; e.act = act; e.mask_ld = ((int)k->g.ldc + 15) / 16 * 16;
+      if (colbias) { e.d = (const char*)pe->d.primary; e.sd = in[i].s[3]; }
+      if (act == 2) { e.mask = (char*)pe->c.secondary; e.smask = in[i].s[4]; }
+      gc.epi.push_back(e);
+    }
+  }
+  for (GroupedClass& gc : out.cls) {
+    if (gc.table.size() == 1) { own.push_back(gc.member[0]); gc.table.clear(); gc.epi.clear(); gc.member.clear(); }     // a single shape keeps its own tuned kernel family
+    for (GemmGroupDesc& gd : gc.table) { const unsigned long long n = gd.first; gd.first = gc.items; gc.items += n; }
+  }
+  std::sort(own.begin(), own.end());
+  out.own.resize(own.size());
+  for (size_t j = 0; j < own.size(); ++j) {
+    const GroupIn& g = in[own[j]];
+    GroupedOwn& o = out.own[j];
+    o.index = own[j]; o.k = ctx_from_handle(g.kernel);
+    std::memset(&o.param, 0, sizeof(o.param));
+    std::memcpy(&o.param, g.param, g.param_bytes);
+    o.has_brc = (o.k->g.flags & kBrFlags) != 0;              // the count is read for batch-reduce handles only, as run_gemm reads it
+    o.brc = o.has_brc ? *(const unsigned long long*)o.param.op.tertiary : 0;
+    o.b = BatchSpec(); o.b.count = g.count;
+    for (int q = 0; q < 5; ++q) o.b.s[q] = g.s[q];
+  }
+  return true;
+}
+// the own launches, in list order: each reads its batch-reduce count from the copy next to its param
+static void grouped_run_own(GroupedOwn& o) {
+  if (o.has_brc) o.param.op.tertiary = &o.brc;
+  run_gemm(o.k, &o.param, o.b);                       // (validation left (BR)GEMM handles only)
+}
+}  // namespace
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_grouped(const libxsmm_hip_gemm_ext_group* groups, size_t ngroups) {
+  static const char* const fn = "libxsmm_hip_gemm_ext_batch_grouped";
+  if (ngroups == 0) return;
+  if (!groups) { set_error(-2, "%s: groups is NULL but ngroups = %zu", fn, ngroups); return; }
+  std::vector<GroupIn> in(ngroups);
+  for (size_t i = 0; i < ngroups; ++i) in[i] = group_in(groups[i]);
+  bool any = false;
+  if (!grouped_validate(fn, true, in.data(), ngroups, &any) || !any) return;
+  if (stream_is_capturing()) {      // the tables are built and uploaded for this call only
+    set_error(-3, "%s cannot be captured into a graph (its group tables live for the call only): make the list a plan (libxsmm_hip_gemm_ext_group_plan_create) and capture libxsmm_hip_gemm_group_plan_launch", fn);
+    return;
+  }
+  coalesce_flush();
+  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
+  scratch_reset();
+  GroupedBuild gb;
+  if (!grouped_build(in.data(), ngroups, gb, nullptr)) return;
+  for (int c4 = 0; c4 < 4; ++c4) {
+    GroupedClass& gc = gb.cls[c4];
+    if (gc.table.empty()) continue;
+    const int bf16 = c4 & 1, fused = c4 >> 1, n = (int)gc.table.size();
+    int err;
+    if (n <= (fused ? kGroupedFusedInline : kGroupedInline)) {
+      err = fused ? launch_gemm_grouped_fused_inline(gc.table.data(), gc.epi.data(), n, gc.items, bf16, tls().stream) : launch_gemm_grouped_inline(gc.table.data(), n, gc.items, bf16, tls().stream);
+    } else {
+      const GemmGroupDesc* dev = (const GemmGroupDesc*)stage_host(gc.table.data(), gc.table.size() * sizeof(GemmGroupDesc));
+      if (!dev) return;
+      const GemmGroupEpi* dep = fused ? (const GemmGroupEpi*)stage_host(gc.epi.data(), gc.epi.size() * sizeof(GemmGroupEpi)) : nullptr;
+      if (fused && !dep) return;
+      err = fused ? launch_gemm_grouped_fused(dev, dep, n, gc.items, bf16, tls().stream) : launch_gemm_grouped(dev, n, gc.items, bf16, tls().stream);
+    }
+    finish_launch(err, fused ? gemm_grouped_fused_kernel_name(bf16) : gemm_grouped_kernel_name(bf16));
+  }
+  for (GroupedOwn& o : gb.own) grouped_run_own(o);
+}
+// A plan: the tables of a list resident in device memory of its own, and the host halves of the own launches by value -- a launch validates nothing, builds
+// nothing and uploads nothing, so it can be captured; the operand bases are read from the table on every (re)play.
+struct libxsmm_hip_gemm_group_plan {
+  int device = 0;
+  unsigned int gen = 0;                               // registry generation of the plan's handles (libxsmm_finalize frees them)
+  char* block = nullptr;                              // every table, one allocation
+  struct Cls { const GemmGroupDesc* table = nullptr; const GemmGroupEpi* epi = nullptr; int n = 0; unsigned long long items = 0; } cls[4];
+  std::vector<GroupedOwn> own;
+  int launches = 0;
+};
+static libxsmm_hip_gemm_group_plan* group_plan_create(const char* fn, bool ext, const std::vector<GroupIn>& in) {
+  bool any = false;
+  if (!grouped_validate(fn, ext, in.data(), in.size(), &any)) return nullptr;
+  GroupedBuild gb;
+  if (!grouped_build(in.data(), in.size(), gb, fn)) return nullptr;
+  if (g_device_count <= 0) { set_error(-4, "%s: no HIP device (this backend has no CPU path)", fn); return nullptr; }
+  libxsmm_hip_gemm_group_plan* plan = new libxsmm_hip_gemm_group_plan();
+  if (hipGetDevice(&plan->device) != hipSuccess) { (void)hipGetLastError(); plan->device = 0; }
+  plan->gen = g_generation.load(std::memory_order_acquire);
+  size_t bytes = 0, at[4][2];
+  for (int c4 = 0; c4 < 4; ++c4) {
+    at[c4][0] = bytes; bytes += (gb.cls[c4].table.size() * sizeof(GemmGroupDesc) + 255) & ~(size_t)255;
+    at[c4][1] = bytes; bytes += (gb.cls[c4].epi.size() * sizeof(GemmGroupEpi) + 255) & ~(size_t)255;
+  }
+  if (bytes) {
+    std::vector<char> image(bytes, 0);
+    for (int c4 = 0; c4 < 4; ++c4) {
+      const GroupedClass& gc = gb.cls[c4];
+      if (gc.table.empty()) continue;
+      std::memcpy(image.data() + at[c4][0], gc.table.data(), gc.table.size() * sizeof(GemmGroupDesc));
+      if (!gc.epi.empty()) std::memcpy(image.data() + at[c4][1], gc.epi.data(), gc.epi.size() * sizeof(GemmGroupEpi));
+    }
+    if (!hip_ok(hipMalloc((void**)&plan->block, bytes), "hipMalloc(group plan)")) { delete plan; return nullptr; }
+    if (!hip_ok(hipMemcpy(plan->block, image.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(group plan)")) { (void)hipFree(plan->block); delete plan; return nullptr; }
+    for (int c4 = 0; c4 < 4; ++c4) {
+      const GroupedClass& gc = gb.cls[c4];
+      if (gc.table.empty()) continue;
+      plan->cls[c4].table = (const GemmGroupDesc*)(plan->block + at[c4][0]);
+      plan->cls[c4].epi = gc.epi.empty() ? nullptr : (const GemmGroupEpi*)(plan->block + at[c4][1]);
+      plan->cls[c4].n = (int)gc.table.size(); plan->cls[c4].items = gc.items;
+      ++plan->launches;
+    }
+  }
+  plan->own = std::move(gb.own);
+  for (GroupedOwn& o : plan->own) if (o.has_brc) o.param.op.tertiary = &o.brc;      // (the vector is final: the copies stay where they are)
+  plan->launches += (int)plan->own.size();
+  return plan;
+}
+LIBXSMM_API libxsmm_hip_gemm_group_plan* libxsmm_hip_gemm_group_plan_create(const libxsmm_hip_gemm_group* groups, size_t ngroups) {
+  static const char* const fn = "libxsmm_hip_gemm_group_plan_create";
+  if (!groups && ngroups > 0) { set_error(-2, "%s: groups is NULL but ngroups = %zu", fn, ngroups); return nullptr; }
+  std::vector<GroupIn> in(ngroups);
+  for (size_t i = 0; i < ngroups; ++i) in[i] = group_in(groups[i]);
+  return group_plan_create(fn, false, in);
+}
+LIBXSMM_API libxsmm_hip_gemm_group_plan* libxsmm_hip_gemm_ext_group_plan_create(const libxsmm_hip_gemm_ext_group* groups, size_t ngroups) {
+  static const char* const fn = "libxsmm_hip_gemm_ext_group_plan_create";
+  if (!groups && ngroups > 0) { set_error(-2, "%s: groups is NULL but ngroups = %zu", fn, ngroups); return nullptr; }
+  std::vector<GroupIn> in(ngroups);
+  for (size_t i = 0; i < ngroups; ++i) in[i] = group_in(groups[i]);
+  return group_plan_create(fn, true, in);
+}
+LIBXSMM_API void libxsmm_hip_gemm_group_plan_launch(const libxsmm_hip_gemm_group_plan* plan) {
+  static const char* const fn = "libxsmm_hip_gemm_group_plan_launch";
+  if (!plan) { set_error(-2, "%s: plan is NULL", fn); return; }
+  if (plan->gen != g_generation.load(std::memory_order_acquire)) { set_error(-3, "%s: the plan's kernel handles were released (libxsmm_finalize ran after the plan was created)", fn); return; }
+  int device = 0;
+  if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); device = plan->device; }
+  if (device != plan->device) { set_error(-3, "%s: the plan belongs to device %d, device %d is current", fn, plan->device, device); return; }
+  coalesce_flush();
+  scratch_reset();
+  for (int c4 = 0; c4 < 4; ++c4) {
+    const libxsmm_hip_gemm_group_plan::Cls& pc = plan->cls[c4];
+    if (pc.n == 0) continue;
+    const int bf16 = c4 & 1, fused = c4 >> 1;
+    const int err = fused ? launch_gemm_grouped_fused(pc.table, pc.epi, pc.n, pc.items, bf16, tls().stream) : launch_gemm_grouped(pc.table, pc.n, pc.items, bf16, tls().stream);
+    finish_launch(err, fused ? gemm_grouped_fused_kernel_name(bf16) : gemm_grouped_kernel_name(bf16));
+  }
+  for (const GroupedOwn& o : plan->own) run_gemm(o.k, &o.param, o.b);
+}
+LIBXSMM_API int libxsmm_hip_gemm_group_plan_launches(const libxsmm_hip_gemm_group_plan* plan) {
+  if (!plan) { set_error(-2, "libxsmm_hip_gemm_group_plan_launches: plan is NULL"); return 0; }
+  return plan->launches;
+}
+LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan* plan) {
+  if (!plan) return;
+  if (stream_is_capturing()) {        // the wait below would invalidate the capture, and the graph would replay on freed tables
+    set_error(-3, "libxsmm_hip_gemm_group_plan_destroy: the thread's stream is being captured into a graph (end the capture first; the plan is kept)"); return;
+  }
+  coalesce_flush();
+  if (g_device_count > 0) (void)hip_ok(hipStreamSynchronize(cur_stream()), "hipStreamSynchronize(group plan destroy)");
+  if (plan->block) (void)hipFree(plan->block);
+  delete plan;
 }
 // ---- segments (libxsmm_hip_gemm_batch_reduce_segments): ADDRESS batch-reduce with a count per C block, one launch -------------------------------------
 // The count is the one argument of a BRGEMM call that the reference re-reads on every call [ref: gemm ref :490-492]; here it is seg_ptr[s + 1] - seg_ptr[s].
@@ -2433,14 +2697,10 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
 // The operators of an ext handle as the fused segment kernels take them, decoded as run_gemm decodes them: colbias, and act 0 none, 1 ReLU, 2 ReLU + bitmask,
 // 3 sigmoid.  false (the error is set) for every other operator and for f64 with any.
 static bool segments_operators(const char* fn, const libxsmm_gemm_descriptor& d, int cls, int& colbias_out, int& act) {
-  const bool colbias = d.bin_type == LIBXSMM_MELTW_TYPE_BINARY_ADD && (d.bin_flags & (LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_0 | LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_1));
-  if ((d.bin_type != LIBXSMM_MELTW_TYPE_BINARY_NONE && !colbias) || d.ap_type != 0 || d.bp_type != 0 ||
-      (d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_NONE && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_RELU && d.cp_type != LIBXSMM_MELTW_TYPE_UNARY_SIGMOID)) {
+  if (!fused_operators(d, colbias_out, act)) {
     set_error(-3, "%s: fused operator not taken (column-broadcast BINARY_ADD, cp RELU with or without bitmask, cp SIGMOID only)", fn); return false;
   }
-  colbias_out = colbias ? 1 : 0; act = 0;
-  if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_RELU) act = (d.cp_flags & LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT) ? 2 : 1;
-  else if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_SIGMOID) act = 3;
+  const bool colbias = colbias_out != 0;
   if (cls == 2 && (colbias || act != 0)) { set_error(-3, "%s: f64 ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
   return true;
 }
