@@ -1,5 +1,6 @@
-// gemm_grouped.hpp -- what runtime.cpp and gemm_grouped_kernels.hip share for the FUSED grouped launches (libxsmm_hip_gemm_ext_batch_grouped and the group
-// plans).  The plain table entry (GemmGroupDesc, internal.hpp) keeps its 144 bytes; the epilogue of a fused group is a parallel entry with the same index.
+// gemm_grouped.hpp -- what runtime.cpp and gemm_grouped_kernels.hip share for the grouped launches (libxsmm_hip_gemm_batch_grouped,
+// libxsmm_hip_gemm_ext_batch_grouped and the group plans).  The table entry (GemmGroupDesc, internal.hpp: the segment kernels read one as well) keeps its 144
+// bytes; the epilogue of a fused group is a parallel entry with the same index.
 #pragma once
 #include "internal.hpp"
 
@@ -14,14 +15,20 @@ struct GemmGroupEpi {
   int pad_;
 };
 static_assert(sizeof(GemmGroupEpi) == 48, "the fused grouped kernels' epilogue entry");
-// Fused tables of up to this many groups travel in the kernel arguments: 18 x (144 + 48) bytes are the 3456 bytes of the plain form's 24 x 144.
+// Host tables of up to this many groups travel in the kernel arguments: 24 x 144 bytes plain, and fused 18 x (144 + 48) bytes, the same 3456 bytes.
 // (gemm_grouped_kernels.hip asserts that the argument block stays within the 4 KiB segment)
+constexpr int kGroupedInline = 24;
 constexpr int kGroupedFusedInline = 18;
 
-// table / epi: device copies (groups ordered by `first`)
-int launch_gemm_grouped_fused(const GemmGroupDesc* table, const GemmGroupEpi* epi, int ngroups, unsigned long long items, int bf16, void* stream);
-// host tables, copied into the kernel arguments
-int launch_gemm_grouped_fused_inline(const GemmGroupDesc* host_table, const GemmGroupEpi* host_epi, int ngroups, unsigned long long items, int bf16, void* stream);
-const char* gemm_grouped_fused_kernel_name(int bf16);
+// One launch of a class: `table` holds the groups ordered by `first`, `epi` the parallel epilogue entries of a fused class (NULL: a plain class).
+struct GroupedLaunch {
+  const GemmGroupDesc* table; const GemmGroupEpi* epi;
+  int ngroups;
+  unsigned long long items;                         // work items of the whole table
+  int bf16;
+  bool host;                                        // the tables are host copies for the kernel arguments (at most the inline limit of groups); else device copies
+};
+// *kname: the pointer-table kernel of bf16 x fused, whichever form carries the table
+int launch_gemm_grouped(const GroupedLaunch& l, void* stream, const char** kname);
 
 }  // namespace xamd

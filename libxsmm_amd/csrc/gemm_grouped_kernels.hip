@@ -1,7 +1,9 @@
-// gemm_grouped_kernels.hip -- libxsmm_hip_gemm_batch_grouped: strided batches of SEVERAL (BR)GEMM shapes in one launch.
+// gemm_grouped_kernels.hip -- libxsmm_hip_gemm_batch_grouped, libxsmm_hip_gemm_ext_batch_grouped and the group plans: strided batches of SEVERAL (BR)GEMM
+// shapes in one launch, plain or with the ext ABI's epilogue in the store.  Eight kernels (f32 / bf16 x plain / fused x pointer table / table in the
+// arguments) behind one launcher (launch_gemm_grouped, gemm_grouped.hpp).
 //
 // The host (runtime.cpp) builds one GemmGroupDesc per eligible group -- operands of element 0, element and batch-reduce strides, the shape, the C tile edge
-// chosen for it and the exclusive prefix of its work items -- and uploads the table.  A work item is (group, element, C tile); every wave owns one item at a
+// chosen for it and the exclusive prefix of its work items -- and hands the table over in the kernel arguments, uploaded for the call, or resident (a plan).  A work item is (group, element, C tile); every wave owns one item at a
 // time and grid-strides over the rest.  The wave finds its group by a binary search over the prefix column of the table: the item index is wave-uniform, so
 // the table is read with scalar loads.  Operands go straight from memory to registers; a wave's tile is private (no LDS, no barrier).
 //
@@ -90,49 +92,35 @@ __global__ __launch_bounds__(256) void gemm_grouped_bf16_fused_kernel(const Gemm
 __global__ __launch_bounds__(256) void gemm_grouped_f32_fused_inline_kernel(GroupedFusedInline tab, int ngroups, unsigned long long total) { grouped_body<false>(tab.g, ngroups, total, tab.e); }
 __global__ __launch_bounds__(256) void gemm_grouped_bf16_fused_inline_kernel(GroupedFusedInline tab, int ngroups, unsigned long long total) { grouped_body<true>(tab.g, ngroups, total, tab.e); }
 
-const char* gemm_grouped_fused_kernel_name(int bf16) { return bf16 ? "gemm_grouped_bf16_fused_kernel" : "gemm_grouped_f32_fused_kernel"; }
-int launch_gemm_grouped_fused(const GemmGroupDesc* table, const GemmGroupEpi* epi, int ngroups, unsigned long long items, int bf16, void* stream) {
-  if (ngroups <= 0 || items == 0) return 0;
-  const unsigned int grid = group_grid(items);
+// The one launcher: the instance of bf16 x fused x inline, picked once.  The name reported is the pointer-table kernel's for the inline form too.
+int launch_gemm_grouped(const GroupedLaunch& l, void* stream, const char** kname) {
+  static const char* const kNames[4] = {"gemm_grouped_f32_kernel", "gemm_grouped_bf16_kernel", "gemm_grouped_f32_fused_kernel", "gemm_grouped_bf16_fused_kernel"};
+  const bool fused = l.epi != nullptr;
+  *kname = kNames[(fused ? 2 : 0) + (l.bf16 ? 1 : 0)];
+  if (l.ngroups <= 0 || l.items == 0) return 0;
+  if (l.host && l.ngroups > (fused ? kGroupedFusedInline : kGroupedInline)) return (int)hipErrorInvalidValue;
+  const dim3 grid(group_grid(l.items)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, table, epi, ngroups, items);
-  else hipLaunchKernelGGL(gemm_grouped_f32_fused_kernel, dim3(grid), dim3(256), 0, st, table, epi, ngroups, items);
-  return (int)hipGetLastError();
-}
-int launch_gemm_grouped_fused_inline(const GemmGroupDesc* host_table, const GemmGroupEpi* host_epi, int ngroups, unsigned long long items, int bf16, void* stream) {
-  if (ngroups <= 0 || items == 0) return 0;
-  if (ngroups > kGroupedFusedInline) return (int)hipErrorInvalidValue;
-  GroupedFusedInline tab;
-  std::memset(&tab, 0, sizeof(tab));
-  std::memcpy(tab.g, host_table, (size_t)ngroups * sizeof(GemmGroupDesc));
-  std::memcpy(tab.e, host_epi, (size_t)ngroups * sizeof(GemmGroupEpi));
-  const unsigned int grid = group_grid(items);
-  hipStream_t st = (hipStream_t)stream;
-  if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_fused_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);
-  else hipLaunchKernelGGL(gemm_grouped_f32_fused_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);
-  return (int)hipGetLastError();
-}
-
-const char* gemm_grouped_kernel_name(int bf16) { return bf16 ? "gemm_grouped_bf16_kernel" : "gemm_grouped_f32_kernel"; }
-
-int launch_gemm_grouped(const GemmGroupDesc* table, int ngroups, unsigned long long items, int bf16, void* stream) {
-  if (ngroups <= 0 || items == 0) return 0;
-  const unsigned int grid = group_grid(items);
-  hipStream_t st = (hipStream_t)stream;
-  if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_kernel, dim3(grid), dim3(256), 0, st, table, ngroups, items);
-  else hipLaunchKernelGGL(gemm_grouped_f32_kernel, dim3(grid), dim3(256), 0, st, table, ngroups, items);
-  return (int)hipGetLastError();
-}
-int launch_gemm_grouped_inline(const GemmGroupDesc* host_table, int ngroups, unsigned long long items, int bf16, void* stream) {
-  if (ngroups <= 0 || items == 0) return 0;
-  if (ngroups > kGroupedInline) return (int)hipErrorInvalidValue;
-  GroupedInline tab;
-  std::memset(&tab, 0, sizeof(tab));
-  std::memcpy(tab.g, host_table, (size_t)ngroups * sizeof(GemmGroupDesc));
-  const unsigned int grid = group_grid(items);
-  hipStream_t st = (hipStream_t)stream;
-  if (bf16) hipLaunchKernelGGL(gemm_grouped_bf16_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);
-  else hipLaunchKernelGGL(gemm_grouped_f32_inline_kernel, dim3(grid), dim3(256), 0, st, tab, ngroups, items);
+  if (!l.host) {
+    if (fused) {
+      if (l.bf16) hipLaunchKernelGGL(gemm_grouped_bf16_fused_kernel, grid, block, 0, st, l.table, l.epi, l.ngroups, l.items);
+      else hipLaunchKernelGGL(gemm_grouped_f32_fused_kernel, grid, block, 0, st, l.table, l.epi, l.ngroups, l.items);
+    } else if (l.bf16) hipLaunchKernelGGL(gemm_grouped_bf16_kernel, grid, block, 0, st, l.table, l.ngroups, l.items);
+    else hipLaunchKernelGGL(gemm_grouped_f32_kernel, grid, block, 0, st, l.table, l.ngroups, l.items);
+  } else if (fused) {
+    GroupedFusedInline tab;
+    std::memset(&tab, 0, sizeof(tab));
+    std::memcpy(tab.g, l.table, (size_t)l.ngroups * sizeof(GemmGroupDesc));
+    std::memcpy(tab.e, l.epi, (size_t)l.ngroups * sizeof(GemmGroupEpi));
+    if (l.bf16) hipLaunchKernelGGL(gemm_grouped_bf16_fused_inline_kernel, grid, block, 0, st, tab, l.ngroups, l.items);
+    else hipLaunchKernelGGL(gemm_grouped_f32_fused_inline_kernel, grid, block, 0, st, tab, l.ngroups, l.items);
+  } else {
+    GroupedInline tab;
+    std::memset(&tab, 0, sizeof(tab));
+    std::memcpy(tab.g, l.table, (size_t)l.ngroups * sizeof(GemmGroupDesc));
+    if (l.bf16) hipLaunchKernelGGL(gemm_grouped_bf16_inline_kernel, grid, block, 0, st, tab, l.ngroups, l.items);
+    else hipLaunchKernelGGL(gemm_grouped_f32_inline_kernel, grid, block, 0, st, tab, l.ngroups, l.items);
+  }
   return (int)hipGetLastError();
 }
 

@@ -108,7 +108,8 @@ struct MeltwArgs {
   int nt;                                             // round 6: the launch's operands cannot be cache resident (footprint, streaming hint): non-temporal loads and stores in the streaming kernels
 };
 
-// libxsmm_hip_gemm_batch_grouped: one eligible group as the grouped kernels read it (gemm_grouped_kernels.hip); a table of these is uploaded per call
+// the grouped entries and plans: one eligible group as the grouped kernels read it (gemm_grouped_kernels.hip; the launcher: gemm_grouped.hpp); the segment kernels
+// take one by value for the shape
 struct GemmGroupDesc {
   const char* a; const char* b; char* c;            // `primary` slots of the group's element 0
   long long sa, sb, sc;                             // element byte strides (0: shared)
@@ -310,10 +311,6 @@ bool meltw_supported(const libxsmm_meltw_descriptor& d);
 int launch_mfma_probe(int bf16, const void* operands, int iterations, void* stream, double* flop);
 int launch_brchain_f32(const GemmArgs& args, float* partial, size_t partial_capacity_tiles, int* nslices, void* stream, const char** kernel_name);
 int launch_brsplit_reduce(const GemmArgs& args, const float* partial, int nsplit, void* stream);
-int launch_gemm_grouped(const GemmGroupDesc* table, int ngroups, unsigned long long items, int bf16, void* stream);   // table: device copy, groups ordered by `first`
-constexpr int kGroupedInline = 24;                // tables of up to this many groups travel in the kernel arguments (launch_gemm_grouped_inline: host table)
-int launch_gemm_grouped_inline(const GemmGroupDesc* host_table, int ngroups, unsigned long long items, int bf16, void* stream);
-const char* gemm_grouped_kernel_name(int bf16);
 // the grid of the grouped and the segment kernels (four waves a workgroup, a wave per work item): one wave per item up to 32 768 workgroups (16 rounds of the
 // chip's resident waves); beyond that the waves grid-stride
 inline unsigned int group_grid(unsigned long long items) { return (unsigned int)((items + 3) / 4 < 32768ull ? (items + 3) / 4 : 32768ull); }

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 
@@ -2263,10 +2264,6 @@ static bool fused_operators(const libxsmm_gemm_descriptor& d, int& colbias_out, 
   else if (d.cp_type == LIBXSMM_MELTW_TYPE_UNARY_SIGMOID) act = 3;
   return true;
 }
-// ---- grouped batches (libxsmm_hip_gemm_batch_grouped): several shapes, one launch per precision class --------------------------------------------------
-// A group enters the grouped kernels (gemm_grouped_kernels.hip) when its handle is a plain GEMM or a STRIDE batch-reduce handle of f32 x f32 -> f32 or
-// bf16 x bf16 -> f32 / bf16 (A flat or VNNI-2, B flat, C not VNNI), NN, with no flag beyond beta and the hints; `cls` = 0 (f32) or 1 (bf16).
-static constexpr unsigned long long kGroupedOwnF32Items = 2048;
 // What the grouped and the segment kernels share (gemm_group_tile.hpp), derived from a handle in one place for grouped_eligible and segments_validate: the
 // precision class, the flags every caller takes (beta, VNNI_A and the hints; `own`: the batch-reduce kind, transposes and ABI bits of the caller), the bound of
 // the kernels' 32-bit element offsets, and the GemmGroupDesc fields that depend on the descriptor alone.  Returns the first check that fails, in this order;
@@ -2294,18 +2291,44 @@ static GroupShape group_shape(const libxsmm_gemm_descriptor& d, unsigned int f, 
   g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
   return kGroupShapeOk;
 }
-// (`abi`: LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI for the entries that take ext handles)
-static bool grouped_eligible(const KernelCtx* k, const libxsmm_hip_gemm_group& grp, GemmGroupDesc& g, int& cls, unsigned int abi = 0) {
+// ---- grouped batches (libxsmm_hip_gemm_batch_grouped, libxsmm_hip_gemm_ext_batch_grouped) and group plans (libxsmm_hip_gemm_group_plan_*) ------------------
+// One path behind four users: the plain and the ext entry (grouped_run), and the plans made from a plain or an ext list.  A group that enters the
+// grouped kernels (gemm_grouped_kernels.hip) joins one of four classes -- plain f32, plain bf16, fused f32, fused bf16 (FusedEpilogue tiles, with a
+// GemmGroupEpi entry next to its GemmGroupDesc) -- and every class leaves as one launch (grouped_launch_class); every other group runs as its own strided
+// launch from a copy of its param (GroupedOwn).  grouped_validate holds every refusal, grouped_build the launch rule.
+// The two list structs are {kernel, param, count, strides} with {op, a, b, c} the common prefix of their params, so the functions that walk a list are
+// templates over the struct and read it in place: at 10 000 groups a call spends 27 ns per group on the host, and a common per-group record cost 3 - 4 ns
+// more (measured, DESIGN.md section 8.1: 270 - 278 -> 299 - 321 us per call as a vector of copies, 308 - 313 us as a view with accessors).
+extern "C++" {
+namespace {
+template <typename Group> constexpr bool kExtGroup = std::is_same<Group, libxsmm_hip_gemm_ext_group>::value;
+// what the four public functions that take a list check first
+static bool groups_missing(const char* fn, const void* groups, size_t ngroups) {
+  if (groups || ngroups == 0) return false;
+  set_error(-2, "%s: groups is NULL but ngroups = %zu", fn, ngroups);
+  return true;
+}
+struct GroupedOwn {                                  // a group that runs as its own strided launch: everything the launch reads on the host, by value
+  size_t index; KernelCtx* k; libxsmm_gemm_ext_param param; unsigned long long brc; bool has_brc; BatchSpec b;
+};
+struct GroupedClass { std::vector<GemmGroupDesc> table; std::vector<GemmGroupEpi> epi; std::vector<size_t> member; unsigned long long items = 0; };
+struct GroupedBuild { GroupedClass cls[4]; std::vector<GroupedOwn> own; };       // cls: 0 f32, 1 bf16, 2 fused f32, 3 fused bf16
+constexpr unsigned int kBrFlags = LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE;
+
+// A group enters the grouped kernels when its handle is a plain GEMM or a STRIDE batch-reduce handle of f32 x f32 -> f32 or bf16 x bf16 -> f32 / bf16 (A flat
+// or VNNI-2, B flat, C not VNNI), NN, with no flag beyond beta and the hints (an ext handle: and the ext ABI bit); `cls` = 0 (f32) or 1 (bf16).  On success `g`
+// is the group's table entry, `first` still its item count.
+template <typename Group> static bool grouped_eligible(const KernelCtx* k, const Group& grp, GemmGroupDesc& g, int& cls) {
   if (k->kind != K_GEMM) return false;
   const libxsmm_gemm_descriptor& d = k->g;
   const unsigned int f = effective_gemm_flags(d);
-  if (group_shape(d, f, LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE | abi, g, cls) != kGroupShapeOk || cls == 2) return false;
-  const libxsmm_gemm_param& p = grp.param;
+  if (group_shape(d, f, LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE | (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI), g, cls) != kGroupShapeOk || cls == 2) return false;
+  const libxsmm_gemm_param& p = *(const libxsmm_gemm_param*)&grp.param;
   if (d.m == 0 || d.n == 0 || d.k == 0 || !p.a.primary || !p.b.primary || !p.c.primary) return false;
   unsigned long long brc = 1;
   if (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) { brc = *(const unsigned long long*)p.op.tertiary; if (brc == 0) return false; }
   const unsigned long long tiles = (unsigned long long)g.tiles_m * (unsigned long long)g.tiles_n;
-  if (grp.count * tiles >= (1ull << 32)) return false;             // the kernels decode a group's items with 32-bit divisions
+  if (grp.count * tiles >= (1ull << 32)) return false;              // the kernels decode a group's items with 32-bit divisions
   g.a = (const char*)p.a.primary; g.b = (const char*)p.b.primary; g.c = (char*)p.c.primary;
   g.sa = grp.stride_a; g.sb = grp.stride_b; g.sc = grp.stride_c;
   g.br_sa = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_a : 0; g.br_sb = (f & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE) ? d.br_stride_b : 0;
@@ -2319,108 +2342,29 @@ static bool grouped_eligible(const KernelCtx* k, const libxsmm_hip_gemm_group& g
   g.first = grp.count * tiles;                          // (the item count: turned into the exclusive prefix when the table is complete)
   return true;
 }
-LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* groups, size_t ngroups) {
-  if (ngroups == 0) return;
-  if (!groups) { set_error(-2, "libxsmm_hip_gemm_batch_grouped: groups is NULL but ngroups = %zu", ngroups); return; }
-  // every group is validated before anything is launched, with the codes libxsmm_hip_gemm_batch_strided sets
-  bool any = false;
-  for (size_t i = 0; i < ngroups; ++i) {
-    const libxsmm_hip_gemm_group& grp = groups[i];
-    KernelCtx* c = ctx_from_handle((const void*)grp.kernel);
-    if (!c) { set_error(-3, "libxsmm_hip_gemm_batch_grouped: group %zu has an unknown kernel handle", i); return; }
-    if (grp.count == 0) continue;
-    if (c->kind != K_GEMM && c->kind != K_SPMM_ASPARSE && c->kind != K_SPMM_BSPARSE) { set_error(-3, "libxsmm_hip_gemm_batch_grouped: group %zu: handle is not a (BR)GEMM or packed sparse kernel", i); return; }
-    if (c->kind == K_GEMM && (c->g.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI)) { set_error(-3, "libxsmm_hip_gemm_batch_grouped: group %zu: ext handles are not taken (use libxsmm_hip_gemm_ext_batch_strided)", i); return; }
-    if (c->kind == K_GEMM && (c->g.flags & (LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE)) && !grp.param.op.tertiary) {
-      set_error(-2, "libxsmm_hip_gemm_batch_grouped: group %zu: BRGEMM handle without op.tertiary (batch-reduce count)", i); return;
-    }
-    any = true;
-  }
-  if (!any) return;
-  {  // the group table is uploaded for this call only: a graph that replayed the launch would read whatever the staging slot holds by then
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (cur_stream() != nullptr && hipStreamIsCapturing(cur_stream(), &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    if (cs != hipStreamCaptureStatusNone) { set_error(-3, "libxsmm_hip_gemm_batch_grouped cannot be captured into a graph (its group table lives for the call only): launch the groups one by one under capture"); return; }
-  }
-  coalesce_flush();
-  if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
-  scratch_reset();
-  std::vector<GemmGroupDesc> table[2];
-  std::vector<size_t> member[2], own;                   // own: groups that run as their own strided launch
-  for (size_t i = 0; i < ngroups; ++i) {
-    if (groups[i].count == 0) continue;
-    GemmGroupDesc gd; int cls = 0;
-    // (grouped_build, further down, holds a copy of this rule and of the single-group rule below for the group plans: change both together)
-    // measured: an f32 group of 2048 work items or more runs at least as fast on its own tuned kernel (p16s, lean, wg64, ragged families:
-    // 1.0 - 2x the grouped kernel's rate at 1024 - 4096 problems) as inside the grouped launch, so it leaves it (gd.first: the group's item count); bf16 groups
-    // gain from the merge and stay
-    if (grouped_eligible(ctx_from_handle((const void*)groups[i].kernel), groups[i], gd, cls) && !(cls == 0 && gd.first >= kGroupedOwnF32Items)) {
-      table[cls].push_back(gd); member[cls].push_back(i);
-    } else own.push_back(i);
-  }
-  for (int cls = 0; cls < 2; ++cls) {
-    if (table[cls].size() == 1) { own.push_back(member[cls][0]); continue; }     // a single shape keeps its own tuned kernel family
-    if (table[cls].empty()) continue;
-    unsigned long long items = 0;
-    for (GemmGroupDesc& gd : table[cls]) { const unsigned long long n = gd.first; gd.first = items; items += n; }
-    int err;
-    if (table[cls].size() <= (size_t)kGroupedInline) err = launch_gemm_grouped_inline(table[cls].data(), (int)table[cls].size(), items, cls, tls().stream);   // in the kernel arguments
-    else {
-      const GemmGroupDesc* dev = (const GemmGroupDesc*)stage_host(table[cls].data(), table[cls].size() * sizeof(GemmGroupDesc));
-      if (!dev) return;
-      err = launch_gemm_grouped(dev, (int)table[cls].size(), items, cls, tls().stream);
-    }
-    finish_launch(err, gemm_grouped_kernel_name(cls));
-  }
-  std::sort(own.begin(), own.end());
-  for (size_t i : own) {
-    const libxsmm_hip_gemm_group& grp = groups[i];
-    KernelCtx* c = ctx_from_handle((const void*)grp.kernel);
-    BatchSpec b; b.count = grp.count; b.s[0] = grp.stride_a; b.s[1] = grp.stride_b; b.s[2] = grp.stride_c;
-    if (c->kind == K_GEMM) run_gemm(c, &grp.param, b); else run_spmm(c, &grp.param, b);
-  }
-}
-// ---- fused grouped batches (libxsmm_hip_gemm_ext_batch_grouped) and group plans (libxsmm_hip_gemm_group_plan_*) ----------------------------------------
-// One list format behind three users: the ext entry, and the plans made from a plain or an ext list.  A group that enters the grouped kernels joins one of
-// four classes -- plain f32, plain bf16 (the kernels of libxsmm_hip_gemm_batch_grouped), fused f32, fused bf16 (FusedEpilogue tiles, with a GemmGroupEpi entry
-// next to its GemmGroupDesc) -- and every class leaves as one launch; every other group runs as its own strided launch from a copy of its param.
-// Measured: a fused f32 group of the plain rule's item count or more is faster on its own ext kernel only on 32-tiles with m and n
-// multiples of 16 (32^3, 48^3, 64^3: 1.2 - 1.5x); the other shapes (13^3, 16^3, 23^3, 40^3, 24 x 48 x 32) run as fast or faster inside the grouped launch and stay.
-static constexpr unsigned long long kGroupedOwnF32FusedItems = 2048;
-namespace {
-struct GroupIn { const void* kernel; const void* param; size_t param_bytes; size_t count; long long s[5]; };
-static GroupIn group_in(const libxsmm_hip_gemm_group& g) { return GroupIn{(const void*)g.kernel, &g.param, sizeof(g.param), g.count, {g.stride_a, g.stride_b, g.stride_c, 0, 0}}; }
-static GroupIn group_in(const libxsmm_hip_gemm_ext_group& g) {
-  return GroupIn{(const void*)g.kernel, &g.param, sizeof(g.param), g.count, {g.stride_a, g.stride_b, g.stride_c, g.stride_d, g.stride_mask}};
-}
-struct GroupedOwn {                                  // a group that runs as its own strided launch: everything the launch reads on the host, by value
-  size_t index; KernelCtx* k; libxsmm_gemm_ext_param param; unsigned long long brc; bool has_brc; BatchSpec b;
-};
-struct GroupedClass { std::vector<GemmGroupDesc> table; std::vector<GemmGroupEpi> epi; std::vector<size_t> member; unsigned long long items = 0; };
-struct GroupedBuild { GroupedClass cls[4]; std::vector<GroupedOwn> own; };       // cls: 0 f32, 1 bf16, 2 fused f32, 3 fused bf16
-constexpr unsigned int kBrFlags = LIBXSMM_GEMM_FLAG_BATCH_REDUCE_ADDRESS | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET | LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE;
-
-// Every group is validated before anything is launched or built.  `ext`: the list holds libxsmm_hip_gemm_ext_group entries (ext handles and only those);
-// else the codes of libxsmm_hip_gemm_batch_grouped.  *any: a group with count > 0 exists.
-static bool grouped_validate(const char* fn, bool ext, const GroupIn* in, size_t ngroups, bool* any) {
+// Every group is validated before anything is launched or built, with the codes libxsmm_hip_gemm_batch_strided sets.  An ext list takes ext handles and
+// only those.  `plan`: a plan is being made (its refusal of an ext handle in a plain list points to the ext form of the caller's own function, the plain
+// entry's to the ext strided entry).  *any: a group with count > 0 exists.
+template <typename Group> static bool grouped_validate(const char* fn, bool plan, const Group* groups, size_t ngroups, bool* any) {
+  constexpr bool ext = kExtGroup<Group>;
   *any = false;
   for (size_t i = 0; i < ngroups; ++i) {
-    KernelCtx* c = ctx_from_handle(in[i].kernel);
+    const Group& g = groups[i];
+    KernelCtx* c = ctx_from_handle((const void*)g.kernel);
     if (!c) { set_error(-3, "%s: group %zu has an unknown kernel handle", fn, i); return false; }
-    if (in[i].count == 0) continue;
+    if (g.count == 0) continue;
     const bool is_ext = c->kind == K_GEMM && (c->g.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI);
     if (ext) {
       if (c->kind != K_GEMM) { set_error(-3, "%s: group %zu: handle is not a BRGEMM kernel (TPP, equation and sparse handles are not taken)", fn, i); return false; }
       if (!is_ext) { set_error(-3, "%s: group %zu: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_grouped)", fn, i); return false; }
     } else {
       if (c->kind != K_GEMM && c->kind != K_SPMM_ASPARSE && c->kind != K_SPMM_BSPARSE) { set_error(-3, "%s: group %zu: handle is not a (BR)GEMM or packed sparse kernel", fn, i); return false; }
-      if (is_ext) { set_error(-3, "%s: group %zu: ext handles are not taken (use the ext form of this call)", fn, i); return false; }
+      if (is_ext) { set_error(-3, "%s: group %zu: ext handles are not taken (use %s)", fn, i, plan ? "the ext form of this call" : "libxsmm_hip_gemm_ext_batch_strided"); return false; }
     }
-    const libxsmm_gemm_param* p = (const libxsmm_gemm_param*)in[i].param;           // {op, a, b, c} is the common prefix of both param structs
-    if (c->kind == K_GEMM && (c->g.flags & kBrFlags) && !p->op.tertiary) { set_error(-2, "%s: group %zu: BRGEMM handle without op.tertiary (batch-reduce count)", fn, i); return false; }
-    if (ext) {
+    if (c->kind == K_GEMM && (c->g.flags & kBrFlags) && !g.param.op.tertiary) { set_error(-2, "%s: group %zu: BRGEMM handle without op.tertiary (batch-reduce count)", fn, i); return false; }
+    if constexpr (ext) {
       const libxsmm_gemm_descriptor& d = c->g;
-      const libxsmm_gemm_ext_param* pe = (const libxsmm_gemm_ext_param*)in[i].param;
+      const libxsmm_gemm_ext_param* pe = &g.param;
       if (d.bin_type == LIBXSMM_MELTW_TYPE_BINARY_ADD && (d.bin_flags & (LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_0 | LIBXSMM_MELTW_FLAG_BINARY_BCAST_COL_IN_1)) && !pe->d.primary) {
         set_error(-2, "%s: group %zu: fused column bias requested but param.d.primary is NULL", fn, i); return false;
       }
@@ -2439,19 +2383,20 @@ static bool stream_is_capturing() {
 }
 // The launch rule over a validated list: classes, the groups that leave them, and the exclusive item prefix of every class table.  `plan_fn` != NULL: a
 // group that cannot enter the grouped kernels at all is refused (-3; false) -- its own launch may stage per-call host data, which a replayed plan cannot redo.
-static bool grouped_build(const GroupIn* in, size_t ngroups, GroupedBuild& out, const char* plan_fn) {
+// Measured: an f32 group of 2048 work items or more runs at least as fast on its own tuned kernel (p16s, lean, wg64, ragged families:
+// 1.0 - 2x the grouped kernel's rate at 1024 - 4096 problems) as inside the grouped launch, so it leaves it; bf16 groups gain from the merge and stay.
+// Measured (section 8.1): a fused f32 group of that item count is faster on its own ext kernel only on 32-tiles with m and n multiples of 16 (32^3, 48^3, 64^3:
+// 1.2 - 1.5x); the other shapes (13^3, 16^3, 23^3, 40^3, 24 x 48 x 32) run as fast or faster inside the grouped launch and stay.
+template <typename Group> static bool grouped_build(const Group* groups, size_t ngroups, GroupedBuild& out, const char* plan_fn) {
+  constexpr unsigned long long kGroupedOwnF32Items = 2048, kGroupedOwnF32FusedItems = 2048;
   std::vector<size_t> own;
   for (size_t i = 0; i < ngroups; ++i) {
-    if (in[i].count == 0) continue;
-    KernelCtx* k = ctx_from_handle(in[i].kernel);
-    libxsmm_hip_gemm_group tg;
-    std::memset(&tg, 0, sizeof(tg));
-    std::memcpy(&tg.param, in[i].param, sizeof(tg.param));
-    tg.count = in[i].count; tg.stride_a = in[i].s[0]; tg.stride_b = in[i].s[1]; tg.stride_c = in[i].s[2];
+    const Group& g = groups[i];
+    if (g.count == 0) continue;
+    KernelCtx* k = ctx_from_handle((const void*)g.kernel);
     GemmGroupDesc gd; int cls = 0, colbias = 0, act = 0;
-    const bool is_ext = k->kind == K_GEMM && (k->g.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI);
-    bool eligible = grouped_eligible(k, tg, gd, cls, is_ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
-    if (eligible && is_ext) eligible = fused_operators(k->g, colbias, act);
+    bool eligible = grouped_eligible(k, g, gd, cls);
+    if constexpr (kExtGroup<Group>) eligible = eligible && fused_operators(k->g, colbias, act);      // (validation left ext handles only; a plain list has none)
     if (!eligible) {
       if (plan_fn) {
         set_error(-3, "%s: group %zu cannot enter the grouped kernels (f32 or bf16, NN, plain or STRIDE batch-reduce with a count above 0, bias / ReLU / sigmoid only): a plan does not take it", plan_fn, i);
@@ -2460,19 +2405,16 @@ static bool grouped_build(const GroupIn* in, size_t ngroups, GroupedBuild& out, 
       own.push_back(i); continue;
     }
     const int c4 = cls + ((colbias || act) ? 2 : 0);
-    // the plain rule (libxsmm_hip_gemm_batch_grouped) and, for fused f32 groups, its measured counterpart: large f32 groups (fused: on 32-tiles with m and n multiples of 16) are faster on their own kernels
-    // (THE PLAIN HALF IS A COPY of the rule in libxsmm_hip_gemm_batch_grouped, which stays as it is: a plain plan equals that call only while the two agree)
     const bool mn16 = gd.tile == 32 && gd.m % 16 == 0 && gd.n % 16 == 0;
-    if ((c4 == 0 && gd.first >= kGroupedOwnF32Items) || (c4 == 2 && gd.first >= kGroupedOwnF32FusedItems && mn16)) { own.push_back(i); continue; }
+    if ((c4 == 0 && gd.first >= kGroupedOwnF32Items) || (c4 == 2 && gd.first >= kGroupedOwnF32FusedItems && mn16)) { own.push_back(i); continue; }   // (gd.first: the group's item count)
     GroupedClass& gc = out.cls[c4];
     gc.table.push_back(gd); gc.member.push_back(i);
-    if (c4 >= 2) {
-      const libxsmm_gemm_ext_param* pe = (const libxsmm_gemm_ext_param*)in[i].param;
+    if constexpr (kExtGroup<Group>) if (c4 >= 2) {
       GemmGroupEpi e;
       std::memset(&e, 0, sizeof(e));
       e.colbias = colbias; e.act = act; e.mask_ld = ((int)k->g.ldc + 15) / 16 * 16;
-      if (colbias) { e.d = (const char*)pe->d.primary; e.sd = in[i].s[3]; }
-      if (act == 2) { e.mask = (char*)pe->c.secondary; e.smask = in[i].s[4]; }
+      if (colbias) { e.d = (const char*)g.param.d.primary; e.sd = g.stride_d; }
+      if (act == 2) { e.mask = (char*)g.param.c.secondary; e.smask = g.stride_mask; }
       gc.epi.push_back(e);
     }
   }
@@ -2483,58 +2425,68 @@ static bool grouped_build(const GroupIn* in, size_t ngroups, GroupedBuild& out, 
   std::sort(own.begin(), own.end());
   out.own.resize(own.size());
   for (size_t j = 0; j < own.size(); ++j) {
-    const GroupIn& g = in[own[j]];
+    const Group& g = groups[own[j]];
     GroupedOwn& o = out.own[j];
-    o.index = own[j]; o.k = ctx_from_handle(g.kernel);
+    o.index = own[j]; o.k = ctx_from_handle((const void*)g.kernel);
     std::memset(&o.param, 0, sizeof(o.param));
-    std::memcpy(&o.param, g.param, g.param_bytes);
-    o.has_brc = (o.k->g.flags & kBrFlags) != 0;              // the count is read for batch-reduce handles only, as run_gemm reads it
+    std::memcpy(&o.param, &g.param, sizeof(g.param));
+    o.has_brc = o.k->kind == K_GEMM && (o.k->g.flags & kBrFlags) != 0;       // the count is read for batch-reduce handles only, as run_gemm reads it
     o.brc = o.has_brc ? *(const unsigned long long*)o.param.op.tertiary : 0;
+    if (o.has_brc) o.param.op.tertiary = &o.brc;            // (the vector is final, and moving it keeps its elements where they are)
     o.b = BatchSpec(); o.b.count = g.count;
-    for (int q = 0; q < 5; ++q) o.b.s[q] = g.s[q];
+    o.b.s[0] = g.stride_a; o.b.s[1] = g.stride_b; o.b.s[2] = g.stride_c;
+    if constexpr (kExtGroup<Group>) { o.b.s[3] = g.stride_d; o.b.s[4] = g.stride_mask; }
   }
   return true;
 }
-// the own launches, in list order: each reads its batch-reduce count from the copy next to its param
-static void grouped_run_own(GroupedOwn& o) {
-  if (o.has_brc) o.param.op.tertiary = &o.brc;
-  run_gemm(o.k, &o.param, o.b);                       // (validation left (BR)GEMM handles only)
+// One class's launch.  `host`: the tables are the call's host vectors -- in the kernel arguments up to the inline limit, else both staged for the call; a
+// plan's resident tables go as they are.  false: staging failed (the error is set).
+static bool grouped_launch_class(int c4, const GemmGroupDesc* table, const GemmGroupEpi* epi, int n, unsigned long long items, bool host) {
+  GroupedLaunch l{table, c4 >= 2 ? epi : nullptr, n, items, c4 & 1, host};
+  if (host && n > (l.epi ? kGroupedFusedInline : kGroupedInline)) {
+    l.table = (const GemmGroupDesc*)stage_host(table, (size_t)n * sizeof(GemmGroupDesc));
+    if (!l.table) return false;
+    if (l.epi && !(l.epi = (const GemmGroupEpi*)stage_host(epi, (size_t)n * sizeof(GemmGroupEpi)))) return false;
+    l.host = false;
+  }
+  const char* kname = nullptr;
+  const int err = launch_gemm_grouped(l, tls().stream, &kname);
+  finish_launch(err, kname);
+  return true;
 }
-}  // namespace
-LIBXSMM_API void libxsmm_hip_gemm_ext_batch_grouped(const libxsmm_hip_gemm_ext_group* groups, size_t ngroups) {
-  static const char* const fn = "libxsmm_hip_gemm_ext_batch_grouped";
-  if (ngroups == 0) return;
-  if (!groups) { set_error(-2, "%s: groups is NULL but ngroups = %zu", fn, ngroups); return; }
-  std::vector<GroupIn> in(ngroups);
-  for (size_t i = 0; i < ngroups; ++i) in[i] = group_in(groups[i]);
+// an own launch: what libxsmm_hip_gemm_batch_strided runs for the handle (validation left (BR)GEMM and, plain lists, packed sparse handles only)
+static void grouped_run_own(const GroupedOwn& o) {
+  if (o.k->kind == K_GEMM) run_gemm(o.k, &o.param, o.b); else run_spmm(o.k, &o.param, o.b);
+}
+// Both entries: every refusal, then the classes f32, bf16, fused f32, fused bf16, then the own launches in list order.
+template <typename Group> static void grouped_run(const char* fn, const Group* groups, size_t ngroups) {
+  constexpr bool ext = kExtGroup<Group>;
+  if (ngroups == 0 || groups_missing(fn, groups, ngroups)) return;
   bool any = false;
-  if (!grouped_validate(fn, true, in.data(), ngroups, &any) || !any) return;
-  if (stream_is_capturing()) {      // the tables are built and uploaded for this call only
-    set_error(-3, "%s cannot be captured into a graph (its group tables live for the call only): make the list a plan (libxsmm_hip_gemm_ext_group_plan_create) and capture libxsmm_hip_gemm_group_plan_launch", fn);
+  if (!grouped_validate(fn, false, groups, ngroups, &any) || !any) return;
+  if (stream_is_capturing()) {      // the tables are built and uploaded for this call only: a graph that replayed the launch would read whatever the staging slot holds by then
+    if (ext) set_error(-3, "%s cannot be captured into a graph (its group tables live for the call only): make the list a plan (libxsmm_hip_gemm_ext_group_plan_create) and capture libxsmm_hip_gemm_group_plan_launch", fn);
+    else set_error(-3, "%s cannot be captured into a graph (its group table lives for the call only): launch the groups one by one under capture", fn);
     return;
   }
   coalesce_flush();
   if (g_device_count <= 0) { set_error(-4, "no HIP device: kernel not launched (this backend has no CPU path)"); return; }
   scratch_reset();
   GroupedBuild gb;
-  if (!grouped_build(in.data(), ngroups, gb, nullptr)) return;
+  if (!grouped_build(groups, ngroups, gb, nullptr)) return;
   for (int c4 = 0; c4 < 4; ++c4) {
-    GroupedClass& gc = gb.cls[c4];
-    if (gc.table.empty()) continue;
-    const int bf16 = c4 & 1, fused = c4 >> 1, n = (int)gc.table.size();
-    int err;
-    if (n <= (fused ? kGroupedFusedInline : kGroupedInline)) {
-      err = fused ? launch_gemm_grouped_fused_inline(gc.table.data(), gc.epi.data(), n, gc.items, bf16, tls().stream) : launch_gemm_grouped_inline(gc.table.data(), n, gc.items, bf16, tls().stream);
-    } else {
-      const GemmGroupDesc* dev = (const GemmGroupDesc*)stage_host(gc.table.data(), gc.table.size() * sizeof(GemmGroupDesc));
-      if (!dev) return;
-      const GemmGroupEpi* dep = fused ? (const GemmGroupEpi*)stage_host(gc.epi.data(), gc.epi.size() * sizeof(GemmGroupEpi)) : nullptr;
-      if (fused && !dep) return;
-      err = fused ? launch_gemm_grouped_fused(dev, dep, n, gc.items, bf16, tls().stream) : launch_gemm_grouped(dev, n, gc.items, bf16, tls().stream);
-    }
-    finish_launch(err, fused ? gemm_grouped_fused_kernel_name(bf16) : gemm_grouped_kernel_name(bf16));
+    const GroupedClass& gc = gb.cls[c4];
+    if (!gc.table.empty() && !grouped_launch_class(c4, gc.table.data(), gc.epi.data(), (int)gc.table.size(), gc.items, true)) return;
   }
-  for (GroupedOwn& o : gb.own) grouped_run_own(o);
+  for (const GroupedOwn& o : gb.own) grouped_run_own(o);
+}
+}  // namespace
+}  // extern "C++"
+LIBXSMM_API void libxsmm_hip_gemm_batch_grouped(const libxsmm_hip_gemm_group* groups, size_t ngroups) {
+  grouped_run("libxsmm_hip_gemm_batch_grouped", groups, ngroups);
+}
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_grouped(const libxsmm_hip_gemm_ext_group* groups, size_t ngroups) {
+  grouped_run("libxsmm_hip_gemm_ext_batch_grouped", groups, ngroups);
 }
 // A plan: the tables of a list resident in device memory of its own, and the host halves of the own launches by value -- a launch validates nothing, builds
 // nothing and uploads nothing, so it can be captured; the operand bases are read from the table on every (re)play.
@@ -2546,11 +2498,11 @@ struct libxsmm_hip_gemm_group_plan {
   std::vector<GroupedOwn> own;
   int launches = 0;
 };
-static libxsmm_hip_gemm_group_plan* group_plan_create(const char* fn, bool ext, const std::vector<GroupIn>& in) {
+extern "C++" template <typename Group> static libxsmm_hip_gemm_group_plan* group_plan_create(const char* fn, const Group* groups, size_t ngroups) {
   bool any = false;
-  if (!grouped_validate(fn, ext, in.data(), in.size(), &any)) return nullptr;
+  if (groups_missing(fn, groups, ngroups) || !grouped_validate(fn, true, groups, ngroups, &any)) return nullptr;
   GroupedBuild gb;
-  if (!grouped_build(in.data(), in.size(), gb, fn)) return nullptr;
+  if (!grouped_build(groups, ngroups, gb, fn)) return nullptr;
   if (g_device_count <= 0) { set_error(-4, "%s: no HIP device (this backend has no CPU path)", fn); return nullptr; }
   libxsmm_hip_gemm_group_plan* plan = new libxsmm_hip_gemm_group_plan();
   if (hipGetDevice(&plan->device) != hipSuccess) { (void)hipGetLastError(); plan->device = 0; }
@@ -2579,24 +2531,15 @@ static libxsmm_hip_gemm_group_plan* group_plan_create(const char* fn, bool ext, 
       ++plan->launches;
     }
   }
-  plan->own = std::move(gb.own);
-  for (GroupedOwn& o : plan->own) if (o.has_brc) o.param.op.tertiary = &o.brc;      // (the vector is final: the copies stay where they are)
+  plan->own = std::move(gb.own);                      // (the batch-reduce counts stay where the params point)
   plan->launches += (int)plan->own.size();
   return plan;
 }
 LIBXSMM_API libxsmm_hip_gemm_group_plan* libxsmm_hip_gemm_group_plan_create(const libxsmm_hip_gemm_group* groups, size_t ngroups) {
-  static const char* const fn = "libxsmm_hip_gemm_group_plan_create";
-  if (!groups && ngroups > 0) { set_error(-2, "%s: groups is NULL but ngroups = %zu", fn, ngroups); return nullptr; }
-  std::vector<GroupIn> in(ngroups);
-  for (size_t i = 0; i < ngroups; ++i) in[i] = group_in(groups[i]);
-  return group_plan_create(fn, false, in);
+  return group_plan_create("libxsmm_hip_gemm_group_plan_create", groups, ngroups);
 }
 LIBXSMM_API libxsmm_hip_gemm_group_plan* libxsmm_hip_gemm_ext_group_plan_create(const libxsmm_hip_gemm_ext_group* groups, size_t ngroups) {
-  static const char* const fn = "libxsmm_hip_gemm_ext_group_plan_create";
-  if (!groups && ngroups > 0) { set_error(-2, "%s: groups is NULL but ngroups = %zu", fn, ngroups); return nullptr; }
-  std::vector<GroupIn> in(ngroups);
-  for (size_t i = 0; i < ngroups; ++i) in[i] = group_in(groups[i]);
-  return group_plan_create(fn, true, in);
+  return group_plan_create("libxsmm_hip_gemm_ext_group_plan_create", groups, ngroups);
 }
 LIBXSMM_API void libxsmm_hip_gemm_group_plan_launch(const libxsmm_hip_gemm_group_plan* plan) {
   static const char* const fn = "libxsmm_hip_gemm_group_plan_launch";
@@ -2609,12 +2552,9 @@ LIBXSMM_API void libxsmm_hip_gemm_group_plan_launch(const libxsmm_hip_gemm_group
   scratch_reset();
   for (int c4 = 0; c4 < 4; ++c4) {
     const libxsmm_hip_gemm_group_plan::Cls& pc = plan->cls[c4];
-    if (pc.n == 0) continue;
-    const int bf16 = c4 & 1, fused = c4 >> 1;
-    const int err = fused ? launch_gemm_grouped_fused(pc.table, pc.epi, pc.n, pc.items, bf16, tls().stream) : launch_gemm_grouped(pc.table, pc.n, pc.items, bf16, tls().stream);
-    finish_launch(err, fused ? gemm_grouped_fused_kernel_name(bf16) : gemm_grouped_kernel_name(bf16));
+    if (pc.n != 0) (void)grouped_launch_class(c4, pc.table, pc.epi, pc.n, pc.items, false);      // resident tables: nothing is staged, nothing fails here
   }
-  for (const GroupedOwn& o : plan->own) run_gemm(o.k, &o.param, o.b);
+  for (const GroupedOwn& o : plan->own) grouped_run_own(o);
 }
 LIBXSMM_API int libxsmm_hip_gemm_group_plan_launches(const libxsmm_hip_gemm_group_plan* plan) {
   if (!plan) { set_error(-2, "libxsmm_hip_gemm_group_plan_launches: plan is NULL"); return 0; }

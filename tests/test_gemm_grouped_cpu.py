@@ -78,6 +78,14 @@ print("ext", run(grp(f32), grp(ext)))
 sys.stderr.write("MARK late_refusal begin\n"); sys.stderr.flush()
 print("late_refusal", run(grp(f32), grp(bf16), grp(br), grp(f64), grp(ext)))
 sys.stderr.write("MARK late_refusal end\n"); sys.stderr.flush()
+# the order of the checks: the first offending group decides, whatever follows it
+def msg():
+    m = api.hip_get_last_error_string().decode(); return m.replace("\n", " ")
+api.hip_gemm_batch_grouped((capi.GemmGroup * 3)(grp(f32), grp(12345), grp(br, brc=False)), 3); print("MSG order_unknown_first", msg()); print("order_unknown_first", err())
+api.hip_gemm_batch_grouped((capi.GemmGroup * 3)(grp(f32), grp(br, brc=False), grp(12345)), 3); print("MSG order_br_first", msg()); print("order_br_first", err())
+# an ext handle: the entry names the ext strided entry, the plain plan the ext form of its own call
+api.hip_gemm_batch_grouped((capi.GemmGroup * 2)(grp(f32), grp(ext)), 2); print("MSG entry_ext", msg()); err()
+p = api.hip_gemm_group_plan_create((capi.GemmGroup * 2)(grp(f32), grp(ext)), 2); print("MSG plan_ext", msg()); print("plan_ext", "%%s/%%d" %% ("null" if not p else "plan", err()))
 print("valid", run(grp(f32), grp(bf16), grp(br), grp(f64)))
 print("valid_one", run(grp(f32)))
 print("launches", api.hip_launch_count(0))
@@ -95,6 +103,7 @@ def test_grouped_entry_refusals_set_the_documented_error_codes(tmp_path):
                    "br_no_count": "-2",          # a BRGEMM handle without op.tertiary
                    "unknown": "-3", "tpp": "-3", "ext": "-3",
                    "late_refusal": "-3",         # the last group is refused ...
+                   "order_unknown_first": "-3", "order_br_first": "-2", "plan_ext": "null/-3",
                    "valid": "-4", "valid_one": "-4",       # accepted; then: no device
                    "launches": "0"}, r.stdout + r.stderr
     # ... and nothing before it was attempted: every error is printed (set_error), and the only one of that call is the refusal -- a call that launched group
@@ -103,3 +112,10 @@ def test_grouped_entry_refusals_set_the_documented_error_codes(tmp_path):
     lines = [ln for ln in err.splitlines() if "ERROR" in ln]
     assert len(lines) == 1 and "ext handles" in lines[0] and "no HIP device" not in err, err
 
+    # the first offending group is the one named, with its own code: unknown handle before a missing count, and the other way round
+    msgs = {ln.split()[1]: ln.split(None, 2)[2] for ln in r.stdout.splitlines() if ln.startswith("MSG ") and len(ln.split()) > 2}
+    assert "group 1" in msgs["order_unknown_first"] and "unknown kernel handle" in msgs["order_unknown_first"], msgs
+    assert "group 1" in msgs["order_br_first"] and "op.tertiary" in msgs["order_br_first"], msgs
+    # the two wordings of the ext-handle refusal, each with its own pointer
+    assert "ext handles are not taken" in msgs["entry_ext"] and "libxsmm_hip_gemm_ext_batch_strided" in msgs["entry_ext"], msgs
+    assert "ext handles are not taken" in msgs["plan_ext"] and "use the ext form of this call" in msgs["plan_ext"], msgs

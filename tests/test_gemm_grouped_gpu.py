@@ -1,8 +1,9 @@
 """libxsmm_hip_gemm_batch_grouped (include/libxsmm_hip.h): several strided (BR)GEMM batches of different shapes in one call equal the loop of
 libxsmm_hip_gemm_batch_strided calls they replace.  f32 groups are bitwise the oracle's k-ordered fmaf chain, bf16 groups lie within the dense kernels'
 tolerance and equal each group's own strided launch bit for bit on exact data; an eligible list of one precision is one launch; fallback groups (other
-types, transposes, pointer-list batch-reduce, packed sparse) equal their own launches; the table search and the grid hold at scale; stream order and
-pipeline sections keep the results.  The last test re-runs the parity tests with every operand flush against unmapped memory (run this file with -x)."""
+types, transposes, pointer-list batch-reduce, packed sparse) equal their own launches; the launch rule turns at its threshold for the entries and their
+plans alike, the table computes the same in the kernel arguments and uploaded, and a captured call is refused; the table search and the grid hold at scale;
+stream order and pipeline sections keep the results.  The last test re-runs the parity tests with every operand flush against unmapped memory (run this file with -x)."""
 import ctypes as C
 import os
 import subprocess
@@ -164,6 +165,135 @@ def test_large_f32_tile32_groups_keep_their_own_kernel():
         ref, _ = g.case.run_oracle(fma=True)
         assert np.array_equal(g.result().view(np.uint32), ref.view(np.uint32))
     assert np.array_equal(big.result().view(np.uint32), big.run_own(api).view(np.uint32))
+
+
+def _fused():
+    """The ext-side helpers (their module imports this one, so they are looked up when a test runs)."""
+    import test_gemm_grouped_fused_gpu as fused
+    return fused
+
+
+def _entry_then_plan(api, direct, planned, ext):
+    """The entry on `direct` and a plan of the same list on `planned`: the launches of the entry, which the plan has to announce and to issue, and the plan's
+    bits, which have to be the entry's."""
+    fused = _fused()
+    arr = ((capi.GemmExtGroup if ext else capi.GemmGroup) * len(direct))(*[g.entry() for g in direct])
+    api.hip_launch_count(1)
+    (api.hip_gemm_ext_batch_grouped if ext else api.hip_gemm_batch_grouped)(arr, len(direct))
+    counted = api.hip_launch_count(1)
+    api.hip_sync(); api.check()
+    plan = fused._plan(api, planned, ext)
+    assert api.hip_gemm_group_plan_launches(plan) == counted
+    api.hip_launch_count(1)
+    api.hip_gemm_group_plan_launch(plan)
+    assert api.hip_launch_count(1) == counted
+    api.hip_sync(); api.check()
+    for i, (a, b) in enumerate(zip(direct, planned)):
+        assert all(np.array_equal(x, y) for x, y in zip(fused._bits(a), fused._bits(b))), f"group {i}: the plan differs from the entry"
+    api.hip_gemm_group_plan_destroy(plan); api.check()
+    return counted
+
+
+@pytest.mark.parametrize("n32,launches", [(2047, 1), (2048, 2)])
+def test_the_f32_rule_turns_at_2048_items_for_the_entry_and_the_plan_alike(n32, launches):
+    """Both sides of the launch rule's threshold (32^3: one item per problem): 2047 problems stay in the grouped launch, 2048 leave for their own kernel --
+    and a plain plan of the same list issues the entry's launches and computes its bits."""
+    api = capi.load()
+    make = lambda: [Group(api, GemmCase(13, 13, 13, batch=5, seed=500)), Group(api, GemmCase(32, 32, 32, batch=n32, seed=501)),
+                    Group(api, GemmCase(16, 16, 16, batch=5, seed=502))]
+    direct, planned = make(), make()
+    assert _entry_then_plan(api, direct, planned, False) == launches
+    for i, g in enumerate(direct):
+        if i == 1 and launches == 2:
+            want = g.run_own(api)                                       # the group that left: bitwise its own strided launch
+        else:
+            want, _ = g.case.run_oracle(fma=True)
+        assert np.array_equal(g.result().view(np.uint32), want.view(np.uint32)), f"group {i}"
+
+
+@pytest.mark.parametrize("n48,launches", [(511, 1), (512, 2)])
+def test_the_fused_f32_rule_turns_at_2048_items_for_the_entry_and_the_plan_alike(n48, launches):
+    """The ext side: 48^3 is four 32-tiles with m and n multiples of 16, so 511 problems (2044 items) stay and 512 (2048 items) leave."""
+    api = capi.load()
+    fused = _fused()
+    make = lambda: [fused.FusedGroup(api, GemmCase(13, 17, 29, colbias=True, act=1, batch=5, seed=510)),
+                    fused.FusedGroup(api, GemmCase(48, 48, 48, colbias=True, act=1, batch=n48, seed=511)),
+                    fused.FusedGroup(api, GemmCase(16, 16, 16, colbias=True, act=1, batch=5, seed=512))]
+    direct, planned = make(), make()
+    assert _entry_then_plan(api, direct, planned, True) == launches
+    for i, g in enumerate(direct):
+        if i == 1 and launches == 2:
+            own, _ = g.run_own(api)
+            assert np.array_equal(g.result().view(np.uint32), own.view(np.uint32)), "the group that left differs from its own ext strided launch"
+        else:
+            fused._assert_chain(g, f"group {i}")
+
+
+INLINE_SHAPES = [(8, 8, 8), (13, 13, 13), (20, 12, 9), (32, 32, 32)]
+
+
+@pytest.mark.parametrize("ngroups", [24, 25])
+def test_plain_tables_at_and_past_the_inline_limit_are_one_launch_and_the_fma_chain(ngroups):
+    """24 groups travel in the kernel arguments, 25 are uploaded: one launch and the same bits either way."""
+    api = capi.load()
+    groups = [Group(api, GemmCase(*INLINE_SHAPES[i % 4], batch=1 + i % 3, seed=600 + i)) for i in range(ngroups)]
+    api.hip_launch_count(1)
+    _grouped(api, [g.entry() for g in groups])
+    assert api.hip_launch_count(1) == 1
+    for i, g in enumerate(groups):
+        ref, _ = g.case.run_oracle(fma=True)
+        assert np.array_equal(g.result().view(np.uint32), ref.view(np.uint32)), f"group {i}"
+
+
+@pytest.mark.parametrize("ngroups", [18, 19])
+def test_fused_tables_at_and_past_the_inline_limit_are_one_launch_and_the_fma_chain(ngroups):
+    """The fused limit: 18 groups (bias + ReLU + bitmask) in the kernel arguments, 19 uploaded; C and masks are the chain's either way."""
+    api = capi.load()
+    fused = _fused()
+    groups = [fused.FusedGroup(api, GemmCase(*INLINE_SHAPES[i % 4], colbias=True, act=2, beta=(i // 4) % 2, batch=1 + i % 3, seed=700 + i), mask_seed=700 + i)
+              for i in range(ngroups)]
+    api.hip_launch_count(1)
+    arr = (capi.GemmExtGroup * ngroups)(*[g.entry() for g in groups])
+    api.hip_gemm_ext_batch_grouped(arr, ngroups)
+    assert api.hip_launch_count(1) == 1
+    api.hip_sync(); api.check()
+    for i, g in enumerate(groups):
+        fused._assert_chain(g, f"group {i}")
+
+
+def test_the_plain_entry_under_capture_is_refused_and_leaves_the_graph_valid():
+    """The group table of a call lives for the call only: under capture the plain entry sets -3, launches nothing and leaves the capture intact -- the plan
+    of the same list, captured next to the refusal, replays to the chain's bits."""
+    import torch
+    api = capi.load()
+    groups = [Group(api, GemmCase(13, 13, 13, batch=5, seed=800)), Group(api, GemmCase(16, 16, 16, batch=5, seed=801))]
+    plan = _fused()._plan(api, groups, False)
+    arr = (capi.GemmGroup * 2)(*[g.entry() for g in groups])
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        api.hip_set_stream(side.cuda_stream)
+        api.hip_launch_count(1)
+        graph.capture_begin()
+        api.hip_gemm_batch_grouped(arr, 2)
+        refused, msg, launched = api.hip_get_last_error(), api.hip_get_last_error_string(), api.hip_launch_count(0)
+        api.hip_clear_last_error()
+        api.hip_gemm_group_plan_launch(plan)
+        graph.capture_end()
+    api.check()
+    torch.cuda.current_stream().wait_stream(side)
+    api.hip_set_stream(None); api.hip_set_async(0)
+    assert refused == -3 and b"one by one" in msg, (refused, msg)
+    assert launched == 0
+    torch.cuda.synchronize()
+    for g in groups:                                                   # nothing ran during the capture
+        assert np.array_equal(g.result().view(np.uint32), g.C0.view(np.uint32))
+    graph.replay(); torch.cuda.synchronize()
+    for i, g in enumerate(groups):
+        ref, _ = g.case.run_oracle(fma=True)
+        assert np.array_equal(g.result().view(np.uint32), ref.view(np.uint32)), f"group {i}"
+    del graph
+    api.hip_gemm_group_plan_destroy(plan); api.check()
 
 
 def _csr_group(api, count=6, M=9, N=7, K=9, P=8, seed=61):
