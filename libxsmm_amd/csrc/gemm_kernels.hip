@@ -3683,14 +3683,15 @@ const char* gemm_kernel_name(const libxsmm_gemm_descriptor& d, bool) {
   return path_name(plan_gemm((int)d.m, (int)d.n, (int)d.k, d.flags, d.a_type, d.b_type, d.c_type, (d.flags & LIBXSMM_GEMM_FLAG_VNNI_C) != 0).path);
 }
 
-template <int MT, int NT, int MODE>
-static void launch_f32(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B;
-  if (!ta && !tb) hipLaunchKernelGGL((gemm_mfma_f32_kernel<MT, NT, false, false, MODE>), grid, dim3(256), 0, st, a);
-  else if (ta && !tb) hipLaunchKernelGGL((gemm_mfma_f32_kernel<MT, NT, true, false, MODE>), grid, dim3(256), 0, st, a);
-  else if (!ta && tb) hipLaunchKernelGGL((gemm_mfma_f32_kernel<MT, NT, false, true, MODE>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((gemm_mfma_f32_kernel<MT, NT, true, true, MODE>), grid, dim3(256), 0, st, a);
-}
+// What the host can know about an operand's alignment: the OR of its base, its batch strides and its STRIDE batch-reduce stride (C: base and stride along i; the
+// sites that also step along j add bs_c2 themselves).  Meaningful for the strided forms only: pointer lists and offset arrays live on the device.
+static unsigned long long a_bits(const GemmArgs& a) { return (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | (unsigned long long)(a.br_mode == 3 ? a.br_stride_a : 0); }
+static unsigned long long b_bits(const GemmArgs& a) { return (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0); }
+static unsigned long long c_bits(const GemmArgs& a) { return (unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c; }
+static bool strided_forms(const GemmArgs& a) { return !a.list_a && a.br_mode != 1 && a.br_mode != 2; }
+static int trans_a(const GemmArgs& a) { return (a.flags & LIBXSMM_GEMM_FLAG_TRANS_A) != 0; }
+static int trans_b(const GemmArgs& a) { return (a.flags & LIBXSMM_GEMM_FLAG_TRANS_B) != 0; }
+
 // The staged path needs every operand tile 16-byte aligned.  That is decidable on the host for the
 // strided forms; pointer lists / offset arrays live on the device and take the direct-load kernel.
 static bool operands_aligned16(const GemmArgs& a, int elem_size) {
@@ -3700,48 +3701,37 @@ static bool operands_aligned16(const GemmArgs& a, int elem_size) {
     const unsigned long long lbits = (unsigned long long)(a.br_mode == 3 ? (a.br_stride_a | a.br_stride_b) : 0) | (unsigned long long)((long long)a.lda * elem_size) | (unsigned long long)((long long)a.ldb * elem_size);
     return (lbits & 15ull) == 0ull;
   }
-  const unsigned long long bits = (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a |
-    (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? (a.br_stride_a | a.br_stride_b) : 0) |
-    (unsigned long long)((long long)a.lda * elem_size) | (unsigned long long)((long long)a.ldb * elem_size);
+  const unsigned long long bits = a_bits(a) | b_bits(a) | (unsigned long long)((long long)a.lda * elem_size) | (unsigned long long)((long long)a.ldb * elem_size);
   return (bits & 15ull) == 0ull;
 }
 
 // ragged bf16 / f16 shapes: every B block and column starts on a dword (strided forms only: the alignment of listed blocks is not known on the host), so that the
 // wave's B panel can be fetched a dword per lane by LDS-DMA (gemm_mfma_bf16_kernel<.., BL = true>); LIBXSMM_HIP_RAGGED16_LDS=0 keeps B in registers (measurement switch)
 static bool ragged16_b_dwords(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || a.list_a || a.br_mode == 1 || a.br_mode == 2 || (a.ldb & 1)) return false;
-  const unsigned long long bits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0);
-  return (bits & 3ull) == 0ull && (unsigned long long)a.n * (unsigned long long)a.ldb < (1ull << 30) && (unsigned long long)a.k * (unsigned long long)a.lda < (1ull << 30);
+  if (!strided_forms(a) || (a.ldb & 1)) return false;
+  return (b_bits(a) & 3ull) == 0ull && (unsigned long long)a.n * (unsigned long long)a.ldb < (1ull << 30) && (unsigned long long)a.k * (unsigned long long)a.lda < (1ull << 30);
 }
 // BND form (round 5: adopted -- bf16 40^3 0.49 -> 0.57, 24^3 0.60 -> 0.70, 72^3 0.35 -> 0.43 of the HBM roofline, profiles/r05_ragged16_switches.jsonl): plain results
 // (beta = 0, no bias, no bitmask, no VNNI C), A blocks on dwords like B's (ragged16_b_dwords), extents that fit a 32-bit buffer resource
 static bool ragged16_bounded(const GemmArgs& a) {
-  const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | (unsigned long long)(a.br_mode == 3 ? a.br_stride_a : 0);
-  return (abits & 3ull) == 0ull && (a.flags & LIBXSMM_GEMM_FLAG_BETA_0) && !a.colbias && a.act != 2 && !a.relu_mask && !a.vnni_c && (unsigned long long)a.n * (unsigned long long)a.ldc < (1ull << 29);
+  return (a_bits(a) & 3ull) == 0ull && (a.flags & LIBXSMM_GEMM_FLAG_BETA_0) && !a.colbias && a.act != 2 && !a.relu_mask && !a.vnni_c && (unsigned long long)a.n * (unsigned long long)a.ldc < (1ull << 29);
 }
 // one masked tile, blobs of at most 1024 dwords, dword-aligned operands, no transposes
 static bool f32_blob_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || (a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B))) return false;
+  if (a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) return false;
   return a.m <= 32 && a.n <= 32 && a.k <= 32 && a.lda <= 32 && a.ldb <= 32 && a.k * a.lda <= 1024 && a.n * a.ldb <= 1024;
 }
 // the lean streaming kernel: one 32x32 tile per problem, 1-D strided batch, plain or STRIDE batch-reduce with at least one block,
 // beta = 0, no fused epilogue, every 32-bit offset inside a tile representable
 static bool f32_lean_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || a.m != 32 || a.n != 32 || a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3) || a.br_count < 1) return false;
+  if (a.m != 32 || a.n != 32 || a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3) || a.br_count < 1) return false;
   if (!(a.flags & LIBXSMM_GEMM_FLAG_BETA_0) || a.colbias || a.act || a.vnni_c) return false;
-  if ((((unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c) & 3ull) != 0) return false;
+  if ((c_bits(a) & 3ull) != 0) return false;
   return a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22) && a.br_count * (unsigned long long)(a.k >> 5) < (1ull << 31);
 }
-// the workgroup-cooperative blocked kernel: 2-D batch whose grid divides into 128 x 128 macro tiles, square 32^3 / 64^3 problems,
-// no transposes, plain or STRIDE batch-reduce, 16-byte aligned operands, 32-bit offsets inside a block
-// the blocked kernel on 16 x 16 x K tiles: grid divisible into 8 x 8 problems, an even number of 16-deep sub-steps, plain epilogue, f32, NN, strided
 // macro-tile kernel (gemm_bf16_macro_kernel): 16 / 32 / 64 tiles; every request offset (lane part + stage part) must fit 32 bits
 static bool bf16_macro_ok(const GemmArgs& a, bool& k16) {
-  constexpr bool off = false;
-  if (off || !a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3) || a.br_count == 0) return false;
+  if (!a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3) || a.br_count == 0) return false;
   const bool f16 = a.a_type == LIBXSMM_DATATYPE_F16;            // IEEE halves: same layouts, v_mfma_f32_32x32x16_f16 (64 / 32 tiles, f32 accumulation only)
   if ((a.a_type != LIBXSMM_DATATYPE_BF16 && !f16) || a.b_type != a.a_type || !(a.flags & LIBXSMM_GEMM_FLAG_VNNI_A)) return false;
   if ((a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B | LIBXSMM_GEMM_FLAG_VNNI_B)) || a.vnni_c || a.colbias || a.act || !(a.flags & LIBXSMM_GEMM_FLAG_BETA_0)) return false;
@@ -3755,36 +3745,34 @@ static bool bf16_macro_ok(const GemmArgs& a, bool& k16) {
   if (ni % ppm || nj % ppm || stages >= (1ull << 31)) return false;
   const unsigned long long bra = a.br_mode == 3 ? (unsigned long long)a.br_stride_a : 0ull, brb = a.br_mode == 3 ? (unsigned long long)a.br_stride_b : 0ull;
   if (a.bs_a < 0 || a.bs_b < 0 || (a.br_mode == 3 && (a.br_stride_a < 0 || a.br_stride_b < 0))) return false;
-  const unsigned long long bits = (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a | (unsigned long long)a.bs_b | bra | brb |
-    (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 2);
+  const unsigned long long bits = a_bits(a) | b_bits(a) | (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 2);
   if ((bits & 15ull) != 0ull || a.lda >= (1 << 20) || a.ldb >= (1 << 20)) return false;
   // largest byte offset a request can form inside the macro tile's operand panel: (ppm - 1) problems + the whole chain + one stage
   const unsigned long long spanA = (unsigned long long)(ppm - 1u) * (unsigned long long)a.bs_a + a.br_count * bra + (unsigned long long)a.k * (unsigned long long)a.lda * 2ull + 4096ull;
   const unsigned long long spanB = (unsigned long long)(ppm - 1u) * (unsigned long long)a.bs_b + a.br_count * brb + (unsigned long long)a.m * (unsigned long long)a.ldb * 2ull + 4096ull;
   return spanA < (1ull << 32) && spanB < (1ull << 32);
 }
+// the blocked kernel on 16 x 16 x K tiles: grid divisible into 8 x 8 problems, an even number of 16-deep sub-steps, plain epilogue, f32, NN, strided
 static bool f32_blocked16_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || !a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3) || a.a_type != LIBXSMM_DATATYPE_F32 || a.b_type != LIBXSMM_DATATYPE_F32 || a.c_type != LIBXSMM_DATATYPE_F32) return false;
+  if (!a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3) || a.a_type != LIBXSMM_DATATYPE_F32 || a.b_type != LIBXSMM_DATATYPE_F32 || a.c_type != LIBXSMM_DATATYPE_F32) return false;
   if ((a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) || a.vnni_c || !(a.flags & LIBXSMM_GEMM_FLAG_BETA_0) || a.colbias || a.act) return false;
   if (a.m != 16 || a.n != 16 || a.k <= 0 || (a.k % 16) != 0) return false;
   const unsigned long long subs = a.br_count * (unsigned long long)(a.k / 16);
   if (subs == 0 || (subs & 1ull) || subs >= (1ull << 31)) return false;
   const unsigned int ni = a.batch_inner, nj = a.nbatch / a.batch_inner;
   if (ni % 8u || nj % 8u) return false;
-  const unsigned long long bits = (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a | (unsigned long long)a.bs_b |
-    (unsigned long long)(a.br_mode == 3 ? (a.br_stride_a | a.br_stride_b) : 0) | (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 4);
+  const unsigned long long bits = a_bits(a) | b_bits(a) | (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 4);
   return (bits & 15ull) == 0ull && a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22);
 }
+// the workgroup-cooperative blocked kernel: 2-D batch whose grid divides into 128 x 128 macro tiles, square 32^3 / 64^3 problems,
+// no transposes, plain or STRIDE batch-reduce, 16-byte aligned operands, 32-bit offsets inside a block
 static bool f32_blocked_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || !a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3)) return false;
+  if (!a.batch_inner || a.list_a || (a.br_mode != 0 && a.br_mode != 3)) return false;
   if ((a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) || a.vnni_c) return false;
   if (!((a.m == 32 && a.n == 32) || (a.m == 64 && a.n == 64)) || (a.k % 32) != 0 || a.k <= 0) return false;
   const unsigned int ppw = 4 / (a.m / 32), ni = a.batch_inner, nj = a.nbatch / a.batch_inner;
   if (ni % ppw || nj % ppw) return false;
-  const unsigned long long bits = (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a | (unsigned long long)a.bs_b |
-    (unsigned long long)(a.br_mode == 3 ? (a.br_stride_a | a.br_stride_b) : 0) | (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 4);
+  const unsigned long long bits = a_bits(a) | b_bits(a) | (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 4);
   return (bits & 15ull) == 0ull && a.lda < (1 << 22) && a.ldb < (1 << 22);
 }
 // Non-temporal operand loads for the streaming kernels?  The calling thread's hint decides (libxsmm_hip_set_streaming_hint), by default the
@@ -3804,34 +3792,29 @@ static bool stream_nt(const GemmArgs& a, int elem_bytes_ab, int elem_bytes_c) {
 // the four-problems-per-wave kernel for 16 x 16 problems: m = n = 16, k % 16 == 0, no transposes, beta = 0, no fused epilogue, operands whose
 // vector loads are aligned (B columns and C columns 16 bytes for f32, 8 bytes for bf16; bf16 A in VNNI-2 with dword-aligned rows)
 static bool p16_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || a.m != 16 || a.n != 16 || a.k <= 0 || (a.k % 16) != 0 || a.vnni_c || a.colbias || a.act) return false;
+  if (a.m != 16 || a.n != 16 || a.k <= 0 || (a.k % 16) != 0 || a.vnni_c || a.colbias || a.act) return false;
   if (!(a.flags & LIBXSMM_GEMM_FLAG_BETA_0) || (a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B | LIBXSMM_GEMM_FLAG_VNNI_B))) return false;
-  if (a.br_mode == 1 || a.br_mode == 2 || a.list_a) return false;            // strided forms only: alignment is decidable on the host
+  if (!strided_forms(a)) return false;            // strided forms only: alignment is decidable on the host
   const bool f32 = a.a_type == LIBXSMM_DATATYPE_F32 && a.b_type == LIBXSMM_DATATYPE_F32 && a.c_type == LIBXSMM_DATATYPE_F32 && !(a.flags & LIBXSMM_GEMM_FLAG_VNNI_A);
   const bool bf16 = a.a_type == LIBXSMM_DATATYPE_BF16 && a.b_type == LIBXSMM_DATATYPE_BF16 && (a.flags & LIBXSMM_GEMM_FLAG_VNNI_A) &&
     (a.c_type == LIBXSMM_DATATYPE_BF16 || a.c_type == LIBXSMM_DATATYPE_F32);
   if (!f32 && !bf16) return false;
   const unsigned long long brs = a.br_mode == 3 ? (unsigned long long)(a.br_stride_a | a.br_stride_b) : 0ull;
   const unsigned long long eb = f32 ? 4ull : 2ull, ec = a.c_type == LIBXSMM_DATATYPE_F32 ? 4ull : 2ull;
-  const unsigned long long bbits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (a.br_mode == 3 ? (unsigned long long)a.br_stride_b : 0ull) | (unsigned long long)a.ldb * eb;
-  const unsigned long long cbits = (unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c | (unsigned long long)a.bs_c2 | (unsigned long long)a.ldc * ec;
-  const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | brs;
+  const unsigned long long bbits = b_bits(a) | (unsigned long long)a.ldb * eb;
+  const unsigned long long cbits = c_bits(a) | (unsigned long long)a.bs_c2 | (unsigned long long)a.ldc * ec;
+  const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | brs;      // (A with both batch-reduce strides: written out)
   if (f32) return (bbits & 15ull) == 0 && (cbits & 15ull) == 0 && (abits & 3ull) == 0;
   return (bbits & 7ull) == 0 && (cbits & (ec == 4 ? 15ull : 7ull)) == 0 && (abits & 3ull) == 0;
 }
 static bool f32_wg64_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || (a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) || a.list_a || (a.br_mode != 0 && a.br_mode != 3)) return false;
+  if ((a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B)) || a.list_a || (a.br_mode != 0 && a.br_mode != 3)) return false;
   return a.lda < (1 << 22) && a.ldb < (1 << 22) && a.k >= 32 && a.br_count * (unsigned long long)(a.k >> 5) < (1ull << 31);
 }
 // bf16 64 x 64 problems, one per workgroup: VNNI-2 A with 16-byte aligned rows (lda % 4 == 0), flat B with 16-byte aligned columns, strided forms
 static bool bf16_wg64_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || a.list_a || (a.br_mode != 0 && a.br_mode != 3)) return false;
-  const unsigned long long brs = a.br_mode == 3 ? (unsigned long long)(a.br_stride_a | a.br_stride_b) : 0ull;
-  const unsigned long long bits = (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a | (unsigned long long)a.bs_b | brs |
-    (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 2);
+  if (a.list_a || (a.br_mode != 0 && a.br_mode != 3)) return false;
+  const unsigned long long bits = a_bits(a) | b_bits(a) | (unsigned long long)((long long)a.lda * 4) | (unsigned long long)((long long)a.ldb * 2);
   return (bits & 15ull) == 0 && a.lda < (1 << 22) && a.ldb < (1 << 22) && a.k >= 32 && a.br_count * (unsigned long long)(a.k >> 5) < (1ull << 31);
 }
 // rounds per operand of the instantiation that serves (waves, tile pairs per wave, rounds needed) -- see the dispatch in launch_gemm
@@ -3843,8 +3826,7 @@ static unsigned int ragged_rounds_cap(int waves, int np, unsigned int rounds) {
 }
 // the ragged kernel: f32 NN with a plain epilogue, 2 <= m <= 128, n <= 128, at most 24 tile pairs; fills in the chunk plan
 static bool f32_ragged_plan(const GemmArgs& a, RaggedCfg& c, int& waves, int& np, int& rounds, unsigned int& lds_bytes, bool& single) {
-  constexpr bool off = false;
-  if (off || a.a_type != LIBXSMM_DATATYPE_F32 || a.b_type != LIBXSMM_DATATYPE_F32 || a.c_type != LIBXSMM_DATATYPE_F32) return false;
+  if (a.a_type != LIBXSMM_DATATYPE_F32 || a.b_type != LIBXSMM_DATATYPE_F32 || a.c_type != LIBXSMM_DATATYPE_F32) return false;
   if ((a.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B | LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_VNNI_B)) || a.vnni_c || a.colbias || a.act) return false;
   // leading dimensions below 2^20: every round offset (columns x leading dimension x 4 bytes) stays below 2^31
   if (a.m < 2 || a.m > 128 || a.n < 1 || a.n > 128 || a.k < 1 || a.lda >= (1 << 20) || a.ldb >= (1 << 20) || a.ldc >= (1 << 20)) return false;
@@ -3902,17 +3884,13 @@ static void launch_ragged(const GemmArgs& a, const RaggedCfg& c, unsigned int ld
   else if (beta0) hipLaunchKernelGGL((gemm_f32_ragged_kernel<W, NP, R2, false, false>), dim3(a.nbatch), dim3(64 * W), lds_bytes, st, a, c);
   else hipLaunchKernelGGL((gemm_f32_ragged_kernel<W, NP, R2, true, false>), dim3(a.nbatch), dim3(64 * W), lds_bytes, st, a, c);
 }
-// the bf16 blocked kernel: 2-D batch of 64 x 64 x K problems (K % 32 == 0) whose grid divides into 4 x 4 problems, VNNI-2 A, flat B, plain
-// epilogue, beta = 0, strided forms, 16-byte aligned rows / columns, at least one block
 static int f32_dma_mode() {   // LIBXSMM_HIP_F32_DMA: 0 never, 1 (default) 64x64 tiles, 2 also 32x32 tiles
   constexpr int mode = 1;
   return mode;
 }
-// B columns 16-byte aligned, A rows dword aligned (always), every offset inside one tile below 4 GiB
 // the bf16 forms kernel: whole 32-tiles, every row of both operand tiles a 16-byte aligned 64- / 128-byte run, strided forms (alignment decidable here)
 static bool bf16_forms_ok(const GemmArgs& a, int& af, int& bf) {
-  constexpr bool off = false;
-  if (off || a.a_type != LIBXSMM_DATATYPE_BF16 || a.b_type != LIBXSMM_DATATYPE_BF16 || (a.c_type != LIBXSMM_DATATYPE_BF16 && a.c_type != LIBXSMM_DATATYPE_F32)) return false;
+  if (a.a_type != LIBXSMM_DATATYPE_BF16 || a.b_type != LIBXSMM_DATATYPE_BF16 || (a.c_type != LIBXSMM_DATATYPE_BF16 && a.c_type != LIBXSMM_DATATYPE_F32)) return false;
   if ((a.m % 32) || (a.n % 32) || (a.k % 32) || a.k <= 0 || a.comp_f16) return false;
   const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B, va = a.flags & LIBXSMM_GEMM_FLAG_VNNI_A, vb = a.flags & LIBXSMM_GEMM_FLAG_VNNI_B;
   if ((va && ta) || (vb && !tb)) return false;
@@ -3925,25 +3903,14 @@ static bool bf16_forms_ok(const GemmArgs& a, int& af, int& bf) {
   if (!a.list_a) bits |= (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a | (unsigned long long)a.bs_b;
   if (a.br_mode == 3) bits |= (unsigned long long)a.br_stride_a | (unsigned long long)a.br_stride_b;
   if (bits & 15ull) return false;
-  if (a.vnni_c && ((((unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c | (unsigned long long)a.bs_c2) & 3ull) != 0)) return false;
+  if (a.vnni_c && (((c_bits(a) | (unsigned long long)a.bs_c2) & 3ull) != 0)) return false;
   return a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22);
 }
-template <int AF, int BF> static void launch_bf16_forms_b(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  if (a.vnni_c) hipLaunchKernelGGL((gemm_bf16_forms_kernel<AF, BF, true>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((gemm_bf16_forms_kernel<AF, BF, false>), grid, dim3(256), 0, st, a);
-}
-template <int AF> static void launch_bf16_forms_a(const GemmArgs& a, int bf, dim3 grid, hipStream_t st) {
-  if (bf == BF_FLAT) launch_bf16_forms_b<AF, BF_FLAT>(a, grid, st); else if (bf == BF_TRANS) launch_bf16_forms_b<AF, BF_TRANS>(a, grid, st); else launch_bf16_forms_b<AF, BF_TVNNI>(a, grid, st);
-}
-
+// the bf16 / f16 streaming kernel: B columns 16-byte aligned, A rows dword aligned (always), every offset inside one tile below 4 GiB
 static bool bf16_stream_ok(const GemmArgs& a) {
-  constexpr bool off = false;
-  if (off || a.list_a || a.br_mode == 1 || a.br_mode == 2) return false;
-  const unsigned long long bits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0) |
-    (unsigned long long)((long long)a.ldb * 2);
-  if (bits & 15ull) return false;
-  const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | (unsigned long long)(a.br_mode == 3 ? a.br_stride_a : 0);
-  if (abits & 3ull) return false;
+  if (!strided_forms(a)) return false;
+  if ((b_bits(a) | (unsigned long long)((long long)a.ldb * 2)) & 15ull) return false;
+  if (a_bits(a) & 3ull) return false;
   return (long long)a.lda * a.k * 2 < (1ll << 31) && (long long)a.ldb * a.n * 2 < (1ll << 31);
 }
 
@@ -4234,10 +4201,9 @@ __global__ __launch_bounds__(256, WGS) void gemm_bitmask16_kernel(GemmArgs p, co
 int launch_gemm_bitmask16(const GemmArgs& a, const void* bitmap, unsigned int* scratch, size_t scratch_bytes, void* stream, const char** name, int* taken) {
   hipStream_t st = (hipStream_t)stream;
   *taken = 0;
-  constexpr bool off = false;
   const bool t16 = (a.a_type == LIBXSMM_DATATYPE_BF16 || a.a_type == LIBXSMM_DATATYPE_F16) && a.b_type == a.a_type;
   // (every 64-column tile of C expands A again: beyond a few tiles the dense image, built once, is the cheaper form)
-  if (off || !t16 || (a.m % 16) || (a.k % 64) || a.m <= 0 || a.n <= 0 || a.n > 256 || a.k <= 0) return 0;
+  if (!t16 || (a.m % 16) || (a.k % 64) || a.m <= 0 || a.n <= 0 || a.n > 256 || a.k <= 0) return 0;
   if ((((size_t)a.b) & 15) || (((long long)a.ldb * 2) & 15) || (((size_t)a.a) & 1) || (((size_t)bitmap) & 3)) return 0;
   const int rows = a.k / 2, row_bytes = a.m / 4, tiles = (a.m + 127) / 128, chunks = a.k / 64;
   if (tiles > 256 || (long long)a.m * a.k >= (1ll << 31)) return 0;
@@ -4311,8 +4277,7 @@ int launch_mfma_probe(int bf16, const void* operands, int iterations, void* stre
 // the partial products of one long f32 chain (see gemm_f32_brchain_kernel); *nslices = partial tiles written; 0 slices = shape not taken
 int launch_brchain_f32(const GemmArgs& a_in, float* partial, size_t partial_capacity_tiles, int* nslices, void* stream, const char** kernel_name) {
   *nslices = 0;
-  constexpr bool off = false;
-  if (off || a_in.a_type != LIBXSMM_DATATYPE_F32 || a_in.b_type != LIBXSMM_DATATYPE_F32 || a_in.br_mode != 3 || (a_in.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B))) return 0;
+  if (a_in.a_type != LIBXSMM_DATATYPE_F32 || a_in.b_type != LIBXSMM_DATATYPE_F32 || a_in.br_mode != 3 || (a_in.flags & (LIBXSMM_GEMM_FLAG_TRANS_A | LIBXSMM_GEMM_FLAG_TRANS_B))) return 0;
   if ((a_in.m % 32) || (a_in.n % 32) || (a_in.k % 32) || a_in.k <= 0 || a_in.m <= 0 || a_in.n <= 0) return 0;
   const unsigned long long bits = (unsigned long long)(size_t)a_in.a | (unsigned long long)(size_t)a_in.b | (unsigned long long)a_in.br_stride_a | (unsigned long long)a_in.br_stride_b |
     (unsigned long long)((long long)a_in.lda * 4) | (unsigned long long)((long long)a_in.ldb * 4);
@@ -4339,545 +4304,532 @@ int launch_brsplit_reduce(const GemmArgs& a, const float* partial, int nsplit, v
   return (int)hipGetLastError();
 }
 
-int launch_gemm(const GemmArgs& a_in, void* stream, const char** kernel_name) {
-  const GemmArgs& a0 = a_in;
-  hipStream_t st = (hipStream_t)stream;
-  if (a0.nbatch == 0 || a0.m <= 0 || a0.n <= 0) { if (kernel_name) *kernel_name = "(empty)"; return 0; }
-  if (a0.a_type == LIBXSMM_DATATYPE_F64 && a0.b_type == LIBXSMM_DATATYPE_F64 && a0.c_type == LIBXSMM_DATATYPE_F64) return launch_gemm_f64(a0, stream, kernel_name);   // gemm_f64_kernels.hip
-  GemmPlan pl_ = plan_gemm(a0.m, a0.n, a0.k, a0.flags, a0.a_type, a0.b_type, a0.c_type, a0.vnni_c);
-  if (a0.comp_f16) pl_ = GemmPlan{P_GENERIC, false};              // a rounding after every product: only the generic kernel does that
-  const GemmPlan pl = pl_;
-  if ((long long)((a0.m + 15) / 16) * ((a0.n + 15) / 16) * (long long)a0.nbatch >= (1ll << 31)) return (int)hipErrorInvalidValue;
-  if (kernel_name) *kernel_name = path_name(pl.path);
-  GemmArgs a = a_in;
-  auto wave_grid = [&](int tm, int tn) {
-    a.tiles_m = (a.m + tm - 1) / tm; a.tiles_n = (a.n + tn - 1) / tn;
-    a.map2d_shift = 0;
-    if (a.batch_inner && a.tiles_m * a.tiles_n == 1) {           // 2-D batch, one tile per element: deal compact super-tiles to the XCDs
-      constexpr int want = 16;
-      const unsigned int ni = a.batch_inner, nj = a.nbatch / a.batch_inner;
-      for (int t = want; t >= 8 && !a.map2d_shift; t >>= 1)
-        if (ni % t == 0 && nj % t == 0 && ((ni / t) * (nj / t)) % 8 == 0) a.map2d_shift = t == 32 ? 5 : (t == 16 ? 4 : 3);
-    }
-    const long long tiles = (long long)a.tiles_m * a.tiles_n * (long long)a.nbatch;
-    return dim3((unsigned int)((tiles + 3) / 4));
-  };
-  dim3 grid;
-  // BF32 on whole 32 x 32 x 32 tiles: the f32 streaming kernel with the operands rounded to bf16 in registers (bit-identical to the reference loop)
-  if (a.a_type == LIBXSMM_DATATYPE_BF32 && a.b_type == LIBXSMM_DATATYPE_BF32 && a.c_type == LIBXSMM_DATATYPE_F32 && (a.m % 32) == 0 && (a.n % 32) == 0 && (a.k % 32) == 0 && a.k > 0 &&
-      !a.vnni_c && !(a.flags & (LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_VNNI_B)) && operands_aligned16(a, 4) && (!a.colbias || ((((unsigned long long)(size_t)a.d | (unsigned long long)a.bs_d) & 3ull) == 0ull)) &&
-      a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22) &&
-      ((((unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c | (unsigned long long)a.bs_c2) & 3ull) == 0ull)) {
-    const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B;
-    grid = wave_grid(32, 32);
-    if (kernel_name) *kernel_name = "gemm_bf32_stream_kernel";
-    if (!ta && !tb) hipLaunchKernelGGL((gemm_f32_stream_kernel<false, false, true>), grid, dim3(256), 0, st, a);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm_f32_stream_kernel<true, false, true>), grid, dim3(256), 0, st, a);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_f32_stream_kernel<false, true, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_f32_stream_kernel<true, true, true>), grid, dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-  }
-  // 2-D batches of f32 16 x 16 x K tiles with a plain epilogue: the blocked kernel on 2 x 2 sub-blocks
-  if (a.batch_inner && f32_blocked16_ok(a)) {
-    a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
-    grid = dim3((a.batch_inner / 8u) * ((a.nbatch / a.batch_inner) / 8u));
-    if (kernel_name) *kernel_name = "gemm_f32_blocked16_kernel";
-    hipLaunchKernelGGL(gemm_f32_blocked16_kernel, grid, dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-  }
-  // 2-D batches of bf16 16^3 / 32 x 32 x K / 64 x 64 x K problems, plain epilogue: the 256 x 256 macro-tile kernel
-  { bool k16 = false;
-    if (a.batch_inner && bf16_macro_ok(a, k16)) {
-      const bool f32c = a.c_type == LIBXSMM_DATATYPE_F32;
-      const bool pack2 = ((a.ldc & 1) == 0) && ((((unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c | (unsigned long long)a.bs_c2) & 3ull) == 0ull);
-      const int form = f32c ? 0 : (pack2 ? 1 : 2);
-      using kfn = void (*)(GemmArgs);
-#define BM_(F_) { gemm_bf16_macro_kernel<F_, 64, false>, gemm_bf16_macro_kernel<F_, 32, false>, gemm_bf16_macro_kernel<F_, 16, false>, gemm_bf16_macro_kernel<F_, 16, true> }
-      static const kfn table[3][4] = { BM_(0), BM_(1), BM_(2) };
-#undef BM_
-      static const bool lds_ok = []() {
-        for (int f = 0; f < 3; ++f) for (int v = 0; v < 4; ++v)
-          if (hipFuncSetAttribute((const void*)table[f][v], hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess) return false;
-        return true; }();
-      if (lds_ok) {
-        const unsigned int ppm = 256u / (unsigned int)a.m;
-        a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
-        const dim3 mgrid((a.batch_inner / ppm) * ((a.nbatch / a.batch_inner) / ppm));
-        if (kernel_name) *kernel_name = "gemm_bf16_macro_kernel";
-        const int v = a.m == 64 ? 0 : (a.m == 32 ? 1 : (k16 ? 3 : 2));
-        if (a.a_type == LIBXSMM_DATATYPE_F16) {       // packed f16 or f32 C (element-wise f16 stores: the single-problem kernels)
-          if (form == 2) goto no_macro;
-          using k16fn = void (*)(GemmArgs);
-          static const k16fn f16_table[2][2] = {{gemm_bf16_macro_kernel<0, 64, false, 4, 4, 4, 0, true>, gemm_bf16_macro_kernel<0, 32, false, 4, 4, 4, 0, true>},
-                                                {gemm_bf16_macro_kernel<1, 64, false, 4, 4, 4, 0, true>, gemm_bf16_macro_kernel<1, 32, false, 4, 4, 4, 0, true>}};
-          static const bool f16_ok = []() {
-            for (int f = 0; f < 2; ++f)
-              for (int w = 0; w < 2; ++w) { if (hipFuncSetAttribute((const void*)f16_table[f][w], hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess) return false; }
-            return true; }();
-          if (!f16_ok) { (void)hipGetLastError(); goto no_macro; }
-          if (kernel_name) *kernel_name = "gemm_f16_macro_kernel";
-          hipLaunchKernelGGL(f16_table[form][v], mgrid, dim3(256), 131072, st, a);
-          return (int)hipGetLastError();
-        }
-#ifdef LIBXSMM_HIP_EXPERIMENTS      // make -C libxsmm_amd/csrc EXPERIMENTS=1: the ablations / wave layouts of profiles/r03_bf16_macro_ablation.txt (tools/bb_ablate.sh)
-        static const int abl = []() { const char* e = getenv("LIBXSMM_HIP_BB_ABL"); return e ? atoi(e) : 0; }();      // timing experiments (wrong results)
-        static const int shape = []() { const char* e = getenv("LIBXSMM_HIP_BM_SHAPE"); return e ? atoi(e) : 0; }();   // experiments: 824 = 8 waves of 2 x 4 tiles, 842 = 4 x 2
-        if ((abl || shape) && form == 1 && v == 0) {
-#define BM_VAR_(NW_, TI_, TJ_, V_) { static const bool ok = hipFuncSetAttribute((const void*)gemm_bf16_macro_kernel<1, 64, false, NW_, TI_, TJ_, V_>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072) == hipSuccess; \
-            if (ok) { hipLaunchKernelGGL((gemm_bf16_macro_kernel<1, 64, false, NW_, TI_, TJ_, V_>), mgrid, dim3(64 * NW_), 131072, st, a); return (int)hipGetLastError(); } }
-          if (shape == 824 && abl == 0) BM_VAR_(8, 2, 4, 0)
-          else if (shape == 842 && abl == 0) BM_VAR_(8, 4, 2, 0)
-          else if (shape == 824 && abl == 3) BM_VAR_(8, 2, 4, 3)
-          else if (shape == 0 && abl == 1) BM_VAR_(4, 4, 4, 1)
-          else if (shape == 0 && abl == 2) BM_VAR_(4, 4, 4, 2)
-          else if (shape == 0 && abl == 3) BM_VAR_(4, 4, 4, 3)
-#undef BM_VAR_
-        }
-#endif
-        hipLaunchKernelGGL(table[form][v], mgrid, dim3(256), 131072, st, a);
-        return (int)hipGetLastError();
-      }
-      (void)hipGetLastError();
-    }
-  }
-  no_macro:
-  // 16 x 16 problems with a plain epilogue: four problems per wave
-  if (p16_ok(a)) {
-    const bool bf16 = a.a_type == LIBXSMM_DATATYPE_BF16;
-    a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
-    // round 4: A through a wave-private LDS image, one 16-byte request per lane (gemm_small_kernels.hip); needs 16-byte aligned A rows
-    { int taken = 0;
-      const int e16 = launch_gemm_p16w(a, stream_nt(a, bf16 ? 2 : 4, a.c_type == LIBXSMM_DATATYPE_F32 ? 4 : 2), stream, kernel_name, &taken);
-      if (taken) return e16; }
-    // small launches are bound by their own latency: keep one problem per wave there (4x the waves), four per wave from 16384 problems on
-    const bool four = a.nbatch >= 16384u;
-    grid = dim3((unsigned int)((a.nbatch + (four ? 15u : 3u)) / (four ? 16u : 4u)));
-    if (kernel_name) *kernel_name = bf16 ? "gemm_bf16_p16_kernel" : "gemm_f32_p16_kernel";
-    if (bf16) { if (four) hipLaunchKernelGGL((gemm_p16_kernel<4, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_p16_kernel<1, true>), grid, dim3(256), 0, st, a); }
-    else { if (four) hipLaunchKernelGGL((gemm_p16_kernel<4, false>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_p16_kernel<1, false>), grid, dim3(256), 0, st, a); }
-    return (int)hipGetLastError();
-  }
-  // 2-D batches of exact f32 32^3 / 64^3 problems (K any multiple of 32), NN, strided: the workgroup-cooperative blocked kernel
-  if (a.batch_inner && (pl.path == P_F32_1x1 || pl.path == P_F32_2x2) && f32_blocked_ok(a)) {
-    const int mb = a.m / 32, ppw = 4 / mb;
+// ------------------------------------------------------------------------------------------------
+// launch_gemm: one launch helper, one launcher per kernel family, and the dispatcher that calls them in their order of precedence.
+// Every kernel launched here except two (gemm_f32_ragged_kernel, gemm_mx4i8_pipe_kernel) is a void(GemmArgs): a family maps its run-time flags to an
+// instantiation through a static table of kernel addresses, written out next to the measured reason for the choice.  A table holds exactly the
+// instantiations of gemm_shards/ (a wider one is an undefined __device_stub__ at link time).
+// A family that may decline follows the protocol of the neighbouring units, int f(..., const char** name, int* taken): *taken = 1 -- launched, the return
+// value is the launch status; 0 -- nothing launched, the next family is asked.  The families behind the switch over the plan's path always launch and
+// return the status.  `name` is never null here (launch_gemm passes a dummy for a caller that does not ask).
+// ------------------------------------------------------------------------------------------------
+using kfn = void (*)(GemmArgs);
+static void launch_tile(kfn kernel, dim3 grid, unsigned int block, unsigned int lds, hipStream_t st, const GemmArgs& a) {
+  hipLaunchKernelGGL(kernel, grid, dim3(block), lds, st, a);
+}
+// the fallback of every family: any type, any layout, any alignment
+static int launch_generic(const GemmArgs& a, hipStream_t st, const char** name) {
+  *name = "gemm_generic_kernel";
+  const long long blocks = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
+  hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)blocks), dim3(64, 4), 0, st, a);
+  return (int)hipGetLastError();
+}
+// one tm x tn tile of C per wave, four waves per workgroup: writes the tile counts and the dealing of a 2-D batch into the arguments, returns the grid
+static dim3 wave_grid(GemmArgs& a, int tm, int tn) {
+  a.tiles_m = (a.m + tm - 1) / tm; a.tiles_n = (a.n + tn - 1) / tn;
+  a.map2d_shift = 0;
+  if (a.batch_inner && a.tiles_m * a.tiles_n == 1) {           // 2-D batch, one tile per element: deal compact super-tiles to the XCDs
+    constexpr int want = 16;
     const unsigned int ni = a.batch_inner, nj = a.nbatch / a.batch_inner;
-    a.tiles_m = a.tiles_n = mb; a.map2d_shift = 0;
-    grid = dim3((ni / ppw) * (nj / ppw));
-    if (mb == 1) { if (kernel_name) *kernel_name = "gemm_f32_blocked_kernel<1>"; hipLaunchKernelGGL((gemm_f32_blocked_kernel<1>), grid, dim3(256), 0, st, a); }
-    else { if (kernel_name) *kernel_name = "gemm_f32_blocked_kernel<2>"; hipLaunchKernelGGL((gemm_f32_blocked_kernel<2>), grid, dim3(256), 0, st, a); }
+    for (int t = want; t >= 8 && !a.map2d_shift; t >>= 1)
+      if (ni % t == 0 && nj % t == 0 && ((ni / t) * (nj / t)) % 8 == 0) a.map2d_shift = t == 32 ? 5 : (t == 16 ? 4 : 3);
+  }
+  const long long tiles = (long long)a.tiles_m * a.tiles_n * (long long)a.nbatch;
+  return dim3((unsigned int)((tiles + 3) / 4));
+}
+static dim3 wave_grid(GemmArgs& a, bool big) { return big ? wave_grid(a, 64, 64) : wave_grid(a, 32, 32); }
+
+// BF32 on whole 32 x 32 x 32 tiles: the f32 streaming kernel with the operands rounded to bf16 in registers (bit-identical to the reference loop)
+static int launch_bf32_stream(GemmArgs& a, const GemmPlan&, hipStream_t st, const char** name, int* taken) {
+  if (!(a.a_type == LIBXSMM_DATATYPE_BF32 && a.b_type == LIBXSMM_DATATYPE_BF32 && a.c_type == LIBXSMM_DATATYPE_F32 && (a.m % 32) == 0 && (a.n % 32) == 0 && (a.k % 32) == 0 && a.k > 0 &&
+        !a.vnni_c && !(a.flags & (LIBXSMM_GEMM_FLAG_VNNI_A | LIBXSMM_GEMM_FLAG_VNNI_B)) && operands_aligned16(a, 4) && (!a.colbias || ((((unsigned long long)(size_t)a.d | (unsigned long long)a.bs_d) & 3ull) == 0ull)) &&
+        a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22) && ((c_bits(a) | (unsigned long long)a.bs_c2) & 3ull) == 0ull)) return 0;
+  static const kfn kernel[2][2] = {{gemm_f32_stream_kernel<false, false, true>, gemm_f32_stream_kernel<false, true, true>},      // [ta][tb]
+                                   {gemm_f32_stream_kernel<true, false, true>, gemm_f32_stream_kernel<true, true, true>}};
+  *taken = 1;
+  *name = "gemm_bf32_stream_kernel";
+  launch_tile(kernel[trans_a(a)][trans_b(a)], wave_grid(a, 32, 32), 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// 2-D batches of f32 16 x 16 x K tiles with a plain epilogue: the blocked kernel on 2 x 2 sub-blocks
+static int launch_f32_blocked16(GemmArgs& a, const GemmPlan&, hipStream_t st, const char** name, int* taken) {
+  if (!a.batch_inner || !f32_blocked16_ok(a)) return 0;
+  *taken = 1;
+  a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
+  *name = "gemm_f32_blocked16_kernel";
+  launch_tile(gemm_f32_blocked16_kernel, dim3((a.batch_inner / 8u) * ((a.nbatch / a.batch_inner) / 8u)), 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// 2-D batches of bf16 16^3 / 32 x 32 x K / 64 x 64 x K problems, plain epilogue: the 256 x 256 macro-tile kernel
+static int launch_bf16_macro(GemmArgs& a, const GemmPlan&, hipStream_t st, const char** name, int* taken) {
+  bool k16 = false;
+  if (!a.batch_inner || !bf16_macro_ok(a, k16)) return 0;
+  const bool f32c = a.c_type == LIBXSMM_DATATYPE_F32;
+  const bool pack2 = ((a.ldc & 1) == 0) && (((c_bits(a) | (unsigned long long)a.bs_c2) & 3ull) == 0ull);
+  const int form = f32c ? 0 : (pack2 ? 1 : 2);
+  static const kfn table[3][4] = {      // [form][64, 32, 16, 16 with k = 16]
+    {gemm_bf16_macro_kernel<0, 64, false>, gemm_bf16_macro_kernel<0, 32, false>, gemm_bf16_macro_kernel<0, 16, false>, gemm_bf16_macro_kernel<0, 16, true>},
+    {gemm_bf16_macro_kernel<1, 64, false>, gemm_bf16_macro_kernel<1, 32, false>, gemm_bf16_macro_kernel<1, 16, false>, gemm_bf16_macro_kernel<1, 16, true>},
+    {gemm_bf16_macro_kernel<2, 64, false>, gemm_bf16_macro_kernel<2, 32, false>, gemm_bf16_macro_kernel<2, 16, false>, gemm_bf16_macro_kernel<2, 16, true>}};
+  static const bool lds_ok = []() {
+    for (int f = 0; f < 3; ++f) for (int v = 0; v < 4; ++v)
+      if (hipFuncSetAttribute((const void*)table[f][v], hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess) return false;
+    return true; }();
+  if (!lds_ok) { (void)hipGetLastError(); return 0; }
+  const unsigned int ppm = 256u / (unsigned int)a.m;
+  a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
+  const dim3 mgrid((a.batch_inner / ppm) * ((a.nbatch / a.batch_inner) / ppm));
+  *name = "gemm_bf16_macro_kernel";
+  const int v = a.m == 64 ? 0 : (a.m == 32 ? 1 : (k16 ? 3 : 2));
+  if (a.a_type == LIBXSMM_DATATYPE_F16) {       // packed f16 or f32 C (element-wise f16 stores: the single-problem kernels)
+    if (form == 2) return 0;
+    static const kfn f16_table[2][2] = {{gemm_bf16_macro_kernel<0, 64, false, 4, 4, 4, 0, true>, gemm_bf16_macro_kernel<0, 32, false, 4, 4, 4, 0, true>},      // [form][64, 32]: no form 2
+                                        {gemm_bf16_macro_kernel<1, 64, false, 4, 4, 4, 0, true>, gemm_bf16_macro_kernel<1, 32, false, 4, 4, 4, 0, true>}};
+    static const bool f16_ok = []() {
+      for (int f = 0; f < 2; ++f)
+        for (int w = 0; w < 2; ++w) { if (hipFuncSetAttribute((const void*)f16_table[f][w], hipFuncAttributeMaxDynamicSharedMemorySize, 131072) != hipSuccess) return false; }
+      return true; }();
+    if (!f16_ok) { (void)hipGetLastError(); return 0; }
+    *taken = 1;
+    *name = "gemm_f16_macro_kernel";
+    launch_tile(f16_table[form][v], mgrid, 256, 131072, st, a);
     return (int)hipGetLastError();
   }
-  // f32 shapes that are not whole 32 / 64 tiles, plain epilogue: persistent workgroups, operands staged in registers, 16 x 16 MFMA tiles
-  // (round 5: shapes of several WHOLE 16-tiles that are not whole 32-tiles -- 48^3, 32 x 48 ... -- ran a wave per 16-tile, nine waves per 48^3 problem that each fetched
-  //  their own panels: 0.49 of the HBM roofline.  The one-problem-per-workgroup kernel takes them like 40^3 and 56^3: 48^3 0.49 -> 0.73, batch 4096 0.41 -> 0.56, beta = 1
-  //  0.53 -> 0.70 (profiles/r05_t16_ragged.jsonl); LIBXSMM_HIP_T16_RAGGED=0: the wave-per-tile kernel)
-  constexpr bool t16_ragged = true;
-  // (whole 32-tiles that are several per problem -- 96^3, 128^3 -- stay a wave per tile: on gemm_wgp_f32_kernel 96^3 0.47 -> 0.49, 128^3 0.47 -> 0.37, r05_t16_ragged.jsonl:
-  //  the f32 matrix pipe is as busy as the memory there)
-  if (((pl.path == P_F32_1x1 || pl.path == P_F32_2x2) && !pl.exact) || (t16_ragged && pl.path == P_F32_T16 && (a.m > 16 || a.n > 16))) {
-    RaggedCfg rc; int waves = 1, np = 1, rounds = 0; unsigned int lds_bytes = 0; bool single = false;
-    if (f32_ragged_plan(a, rc, waves, np, rounds, lds_bytes, single)) {
-      a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
-      if (kernel_name) *kernel_name = "gemm_f32_ragged_kernel";
-      if (waves == 1) {                                      // rounds == ragged_rounds_cap(...): the LDS plan is sized for exactly this instantiation
-        if (rounds == 4) launch_ragged<1, 1, 4>(a, rc, lds_bytes, single, st);
-        else if (rounds == 8 && np == 1) launch_ragged<1, 1, 8>(a, rc, lds_bytes, single, st);
-        else if (rounds == 8) launch_ragged<1, 2, 8>(a, rc, lds_bytes, single, st);
-        else if (rounds == 12) launch_ragged<1, 2, 12>(a, rc, lds_bytes, single, st);
-        else launch_ragged<1, 2, 17>(a, rc, lds_bytes, single, st);
-      } else {
-        if (rounds == 7) launch_ragged<4, 2, 7>(a, rc, lds_bytes, single, st);
-        else if (rounds == 10 && np == 2) launch_ragged<4, 2, 10>(a, rc, lds_bytes, single, st);
-        else if (rounds == 10) launch_ragged<4, 4, 10>(a, rc, lds_bytes, single, st);
-        else if (rounds == 14 && np <= 4) launch_ragged<4, 4, 14>(a, rc, lds_bytes, single, st);
-        else if (rounds == 14) launch_ragged<4, 6, 14>(a, rc, lds_bytes, single, st);
-        else if (np <= 4) launch_ragged<4, 4, 24>(a, rc, lds_bytes, single, st);
-        else launch_ragged<4, 6, 24>(a, rc, lds_bytes, single, st);
-      }
-      return (int)hipGetLastError();
-    }
-    // round 5: what that plan does not hold (72^3 with beta = 1: three images next to the operands; deep K with wide n ...) ran on the wave-per-tile kernel at 0.19 of
-    // the roofline.  When rows of A and columns of B are whole 16-byte pieces: the blocks by LDS-DMA, K in chunks, one problem per workgroup (gemm_wgp_f32_kernels.hip:
-    // 0.43 - 0.48 there).  Where both apply the register-staged kernel is the faster one (72^3 0.51 against 0.41, 40^3 0.66 against 0.56: these shapes are as much
-    // matrix-pipe as memory bound, profiles/r05_wgp_f32.jsonl) and keeps its shapes.
-    { int taken = 0; const int e = launch_gemm_wgp_f32(a, stream, kernel_name, &taken); if (taken) return e; }
+  *taken = 1;
+#ifdef LIBXSMM_HIP_EXPERIMENTS      // make -C libxsmm_amd/csrc EXPERIMENTS=1: the ablations / wave layouts of profiles/r03_bf16_macro_ablation.txt (tools/bb_ablate.sh)
+  static const int abl = []() { const char* e = getenv("LIBXSMM_HIP_BB_ABL"); return e ? atoi(e) : 0; }();      // timing experiments (wrong results)
+  static const int shape = []() { const char* e = getenv("LIBXSMM_HIP_BM_SHAPE"); return e ? atoi(e) : 0; }();   // experiments: 824 = 8 waves of 2 x 4 tiles, 842 = 4 x 2
+  if ((abl || shape) && form == 1 && v == 0) {
+#define BM_VAR_(NW_, TI_, TJ_, V_) { static const bool ok = hipFuncSetAttribute((const void*)gemm_bf16_macro_kernel<1, 64, false, NW_, TI_, TJ_, V_>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072) == hipSuccess; \
+      if (ok) { hipLaunchKernelGGL((gemm_bf16_macro_kernel<1, 64, false, NW_, TI_, TJ_, V_>), mgrid, dim3(64 * NW_), 131072, st, a); return (int)hipGetLastError(); } }
+    if (shape == 824 && abl == 0) BM_VAR_(8, 2, 4, 0)
+    else if (shape == 842 && abl == 0) BM_VAR_(8, 4, 2, 0)
+    else if (shape == 824 && abl == 3) BM_VAR_(8, 2, 4, 3)
+    else if (shape == 0 && abl == 1) BM_VAR_(4, 4, 4, 1)
+    else if (shape == 0 && abl == 2) BM_VAR_(4, 4, 4, 2)
+    else if (shape == 0 && abl == 3) BM_VAR_(4, 4, 4, 3)
+#undef BM_VAR_
   }
-  // bf16 in the other operand forms (flat / transposed A, transposed / VNNI B, VNNI C): operands re-laid out on the way out of a wave-private LDS image (round 4)
-  { int af = 0, bf = 0;
-    if (bf16_forms_ok(a, af, bf)) {
-      grid = wave_grid(32, 32);
-      if (kernel_name) *kernel_name = "gemm_bf16_forms_kernel";
-      if (af == AF_VNNI) launch_bf16_forms_a<AF_VNNI>(a, bf, grid, st); else if (af == AF_FLAT) launch_bf16_forms_a<AF_FLAT>(a, bf, grid, st); else launch_bf16_forms_a<AF_TRANS>(a, bf, grid, st);
-      return (int)hipGetLastError();
-    } }
+#endif
+  launch_tile(table[form][v], mgrid, 256, 131072, st, a);
+  return (int)hipGetLastError();
+}
+
+// 16 x 16 problems with a plain epilogue: four problems per wave
+static int launch_p16(GemmArgs& a, const GemmPlan&, hipStream_t st, const char** name, int* taken) {
+  if (!p16_ok(a)) return 0;
+  *taken = 1;
+  const bool bf16 = a.a_type == LIBXSMM_DATATYPE_BF16;
+  a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
+  // round 4: A through a wave-private LDS image, one 16-byte request per lane (gemm_small_kernels.hip); needs 16-byte aligned A rows
+  { int taken16 = 0;
+    const int e16 = launch_gemm_p16w(a, stream_nt(a, bf16 ? 2 : 4, a.c_type == LIBXSMM_DATATYPE_F32 ? 4 : 2), st, name, &taken16);
+    if (taken16) return e16; }
+  // small launches are bound by their own latency: keep one problem per wave there (4x the waves), four per wave from 16384 problems on
+  const bool four = a.nbatch >= 16384u;
+  static const kfn kernel[2][2] = {{gemm_p16_kernel<1, false>, gemm_p16_kernel<4, false>}, {gemm_p16_kernel<1, true>, gemm_p16_kernel<4, true>}};      // [bf16][four]
+  *name = bf16 ? "gemm_bf16_p16_kernel" : "gemm_f32_p16_kernel";
+  launch_tile(kernel[bf16][four], dim3((unsigned int)((a.nbatch + (four ? 15u : 3u)) / (four ? 16u : 4u))), 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// 2-D batches of exact f32 32^3 / 64^3 problems (K any multiple of 32), NN, strided: the workgroup-cooperative blocked kernel
+static int launch_f32_blocked(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name, int* taken) {
+  if (!(a.batch_inner && (pl.path == P_F32_1x1 || pl.path == P_F32_2x2) && f32_blocked_ok(a))) return 0;
+  *taken = 1;
+  const int mb = a.m / 32, ppw = 4 / mb;
+  const unsigned int ni = a.batch_inner, nj = a.nbatch / a.batch_inner;
+  a.tiles_m = a.tiles_n = mb; a.map2d_shift = 0;
+  static const kfn kernel[2] = {gemm_f32_blocked_kernel<1>, gemm_f32_blocked_kernel<2>};      // [mb - 1]
+  *name = mb == 1 ? "gemm_f32_blocked_kernel<1>" : "gemm_f32_blocked_kernel<2>";
+  launch_tile(kernel[mb == 1 ? 0 : 1], dim3((ni / ppw) * (nj / ppw)), 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// f32 shapes that are not whole 32 / 64 tiles, plain epilogue: persistent workgroups, operands staged in registers, 16 x 16 MFMA tiles
+// (round 5: shapes of several WHOLE 16-tiles that are not whole 32-tiles -- 48^3, 32 x 48 ... -- ran a wave per 16-tile, nine waves per 48^3 problem that each fetched
+//  their own panels: 0.49 of the HBM roofline.  The one-problem-per-workgroup kernel takes them like 40^3 and 56^3: 48^3 0.49 -> 0.73, batch 4096 0.41 -> 0.56, beta = 1
+//  0.53 -> 0.70 (profiles/r05_t16_ragged.jsonl); LIBXSMM_HIP_T16_RAGGED=0: the wave-per-tile kernel)
+// (whole 32-tiles that are several per problem -- 96^3, 128^3 -- stay a wave per tile: on gemm_wgp_f32_kernel 96^3 0.47 -> 0.49, 128^3 0.47 -> 0.37, r05_t16_ragged.jsonl:
+//  the f32 matrix pipe is as busy as the memory there)
+static int launch_f32_ragged(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name, int* taken) {
+  constexpr bool t16_ragged = true;
+  if (!(((pl.path == P_F32_1x1 || pl.path == P_F32_2x2) && !pl.exact) || (t16_ragged && pl.path == P_F32_T16 && (a.m > 16 || a.n > 16)))) return 0;
+  RaggedCfg rc; int waves = 1, np = 1, rounds = 0; unsigned int lds_bytes = 0; bool single = false;
+  if (f32_ragged_plan(a, rc, waves, np, rounds, lds_bytes, single)) {
+    *taken = 1;
+    a.tiles_m = a.tiles_n = 1; a.map2d_shift = 0;
+    *name = "gemm_f32_ragged_kernel";
+    if (waves == 1) {                                      // rounds == ragged_rounds_cap(...): the LDS plan is sized for exactly this instantiation
+      if (rounds == 4) launch_ragged<1, 1, 4>(a, rc, lds_bytes, single, st);
+      else if (rounds == 8 && np == 1) launch_ragged<1, 1, 8>(a, rc, lds_bytes, single, st);
+      else if (rounds == 8) launch_ragged<1, 2, 8>(a, rc, lds_bytes, single, st);
+      else if (rounds == 12) launch_ragged<1, 2, 12>(a, rc, lds_bytes, single, st);
+      else launch_ragged<1, 2, 17>(a, rc, lds_bytes, single, st);
+    } else {
+      if (rounds == 7) launch_ragged<4, 2, 7>(a, rc, lds_bytes, single, st);
+      else if (rounds == 10 && np == 2) launch_ragged<4, 2, 10>(a, rc, lds_bytes, single, st);
+      else if (rounds == 10) launch_ragged<4, 4, 10>(a, rc, lds_bytes, single, st);
+      else if (rounds == 14 && np <= 4) launch_ragged<4, 4, 14>(a, rc, lds_bytes, single, st);
+      else if (rounds == 14) launch_ragged<4, 6, 14>(a, rc, lds_bytes, single, st);
+      else if (np <= 4) launch_ragged<4, 4, 24>(a, rc, lds_bytes, single, st);
+      else launch_ragged<4, 6, 24>(a, rc, lds_bytes, single, st);
+    }
+    return (int)hipGetLastError();
+  }
+  // round 5: what that plan does not hold (72^3 with beta = 1: three images next to the operands; deep K with wide n ...) ran on the wave-per-tile kernel at 0.19 of
+  // the roofline.  When rows of A and columns of B are whole 16-byte pieces: the blocks by LDS-DMA, K in chunks, one problem per workgroup (gemm_wgp_f32_kernels.hip:
+  // 0.43 - 0.48 there).  Where both apply the register-staged kernel is the faster one (72^3 0.51 against 0.41, 40^3 0.66 against 0.56: these shapes are as much
+  // matrix-pipe as memory bound, profiles/r05_wgp_f32.jsonl) and keeps its shapes.
+  return launch_gemm_wgp_f32(a, st, name, taken);
+}
+
+// bf16 in the other operand forms (flat / transposed A, transposed / VNNI B, VNNI C): operands re-laid out on the way out of a wave-private LDS image (round 4)
+static int launch_bf16_forms(GemmArgs& a, const GemmPlan&, hipStream_t st, const char** name, int* taken) {
+  int af = 0, bf = 0;
+  if (!bf16_forms_ok(a, af, bf)) return 0;
+  static const kfn kernel[3][3][2] = {      // [AF_VNNI, AF_FLAT, AF_TRANS][BF_FLAT, BF_TRANS, BF_TVNNI][vnni_c]
+    {{gemm_bf16_forms_kernel<AF_VNNI, BF_FLAT, false>, gemm_bf16_forms_kernel<AF_VNNI, BF_FLAT, true>}, {gemm_bf16_forms_kernel<AF_VNNI, BF_TRANS, false>, gemm_bf16_forms_kernel<AF_VNNI, BF_TRANS, true>},
+     {gemm_bf16_forms_kernel<AF_VNNI, BF_TVNNI, false>, gemm_bf16_forms_kernel<AF_VNNI, BF_TVNNI, true>}},
+    {{gemm_bf16_forms_kernel<AF_FLAT, BF_FLAT, false>, gemm_bf16_forms_kernel<AF_FLAT, BF_FLAT, true>}, {gemm_bf16_forms_kernel<AF_FLAT, BF_TRANS, false>, gemm_bf16_forms_kernel<AF_FLAT, BF_TRANS, true>},
+     {gemm_bf16_forms_kernel<AF_FLAT, BF_TVNNI, false>, gemm_bf16_forms_kernel<AF_FLAT, BF_TVNNI, true>}},
+    {{gemm_bf16_forms_kernel<AF_TRANS, BF_FLAT, false>, gemm_bf16_forms_kernel<AF_TRANS, BF_FLAT, true>}, {gemm_bf16_forms_kernel<AF_TRANS, BF_TRANS, false>, gemm_bf16_forms_kernel<AF_TRANS, BF_TRANS, true>},
+     {gemm_bf16_forms_kernel<AF_TRANS, BF_TVNNI, false>, gemm_bf16_forms_kernel<AF_TRANS, BF_TVNNI, true>}}};
+  static_assert(AF_VNNI == 0 && AF_FLAT == 1 && AF_TRANS == 2 && BF_FLAT == 0 && BF_TRANS == 1 && BF_TVNNI == 2, "the forms index the table");
+  *taken = 1;
+  *name = "gemm_bf16_forms_kernel";
+  launch_tile(kernel[af][bf][a.vnni_c ? 1 : 0], wave_grid(a, 32, 32), 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// 8-bit operands on the masked matrix-core kernel: any shape with whole k-quads, any alignment, any batch-reduce form.  Declines what it does not
+// take (more than 2^31 bytes inside one operand).
+static int launch_m8(GemmArgs& a, bool big, hipStream_t st, const char** name, int* taken) {
+  constexpr int tile_env = 0;      // experiments: 1 forces 32 x 32 tiles, 2 forces 64 x 64
+  if (tile_env == 1) big = false; else if (tile_env == 2) big = true;
+  const bool fp8 = a.a_type == LIBXSMM_DATATYPE_BF8 || a.a_type == LIBXSMM_DATATYPE_HF8;
+  if (fp8 && a.c_type != LIBXSMM_DATATYPE_F32 && a.vnni_c) return 0;
+  if ((a.k & 3) || a.k <= 0) return 0;
+  *taken = 1;
+  const bool ua = a.a_type == LIBXSMM_DATATYPE_U8, ub = a.b_type == LIBXSMM_DATATYPE_U8;
+  // packed operand blocks of several tiles: one problem per workgroup, whole problem in LDS (gemm_wgp8_kernels.hip, round 5); an error of that launch is left
+  // for the hipGetLastError() behind it
+  { int taken8 = 0; (void)launch_gemm_wgp8(a, fp8 ? (a.a_type == LIBXSMM_DATATYPE_HF8 ? 2 : 1) : 0, ua, ub, st, name, &taken8); if (taken8) return (int)hipGetLastError(); }
+  const dim3 grid = wave_grid(a, big);
+  *name = big ? "gemm_mfma_8bit_kernel<2,2>" : "gemm_mfma_8bit_kernel<1,1>";
+  // strided forms whose blocks, rows and columns start on dwords: B through LDS (see the kernel); LIBXSMM_HIP_M8_LDS=0 keeps B in registers (measurement switch)
+  constexpr bool lds_off = false;
+  const bool bl = !lds_off && strided_forms(a) && ((a_bits(a) | b_bits(a) | (unsigned long long)a.ldb) & 3ull) == 0ull &&
+    (unsigned long long)a.n * (unsigned long long)a.ldb < (1ull << 31) && (unsigned long long)a.k * (unsigned long long)a.lda < (1ull << 31);
+  static const kfn kernel[2][6][2] = {      // [2 x 2 tiles][integers: ua + 2 ub, 4 BF8, 5 HF8][bl]
+    {{gemm_mfma_8bit_kernel<1, 1, 0, false, false, false>, gemm_mfma_8bit_kernel<1, 1, 0, false, false, true>}, {gemm_mfma_8bit_kernel<1, 1, 0, true, false, false>, gemm_mfma_8bit_kernel<1, 1, 0, true, false, true>},
+     {gemm_mfma_8bit_kernel<1, 1, 0, false, true, false>, gemm_mfma_8bit_kernel<1, 1, 0, false, true, true>}, {gemm_mfma_8bit_kernel<1, 1, 0, true, true, false>, gemm_mfma_8bit_kernel<1, 1, 0, true, true, true>},
+     {gemm_mfma_8bit_kernel<1, 1, 1, false, false, false>, gemm_mfma_8bit_kernel<1, 1, 1, false, false, true>}, {gemm_mfma_8bit_kernel<1, 1, 2, false, false, false>, gemm_mfma_8bit_kernel<1, 1, 2, false, false, true>}},
+    {{gemm_mfma_8bit_kernel<2, 2, 0, false, false, false>, gemm_mfma_8bit_kernel<2, 2, 0, false, false, true>}, {gemm_mfma_8bit_kernel<2, 2, 0, true, false, false>, gemm_mfma_8bit_kernel<2, 2, 0, true, false, true>},
+     {gemm_mfma_8bit_kernel<2, 2, 0, false, true, false>, gemm_mfma_8bit_kernel<2, 2, 0, false, true, true>}, {gemm_mfma_8bit_kernel<2, 2, 0, true, true, false>, gemm_mfma_8bit_kernel<2, 2, 0, true, true, true>},
+     {gemm_mfma_8bit_kernel<2, 2, 1, false, false, false>, gemm_mfma_8bit_kernel<2, 2, 1, false, false, true>}, {gemm_mfma_8bit_kernel<2, 2, 2, false, false, false>, gemm_mfma_8bit_kernel<2, 2, 2, false, false, true>}}};
+  const int kind = fp8 ? (a.a_type == LIBXSMM_DATATYPE_HF8 ? 5 : 4) : (ua ? 1 : 0) + (ub ? 2 : 0);
+  launch_tile(kernel[big][kind][bl], grid, 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+// a family's way out for unaligned operands, pointer / offset lists: the masked matrix-core kernel, then the generic one
+static int launch_m8_or_generic(GemmArgs& a, bool big, hipStream_t st, const char** name) {
+  int taken = 0;
+  const int e = launch_m8(a, big, st, name, &taken);
+  return taken ? e : launch_generic(a, st, name);
+}
+
+// 8-bit weights x bf16 activations
+static int launch_w8(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  const bool big = pl.path == P_W8_2x2, va8 = (a.flags & LIBXSMM_GEMM_FLAG_VNNI_A) != 0;
+  const int kind = a.a_type == LIBXSMM_DATATYPE_I8 ? 4 : ((a.a_type == LIBXSMM_DATATYPE_HF8 ? 1 : 0) + (va8 ? 0 : 2));
+  // ragged / several-tile shapes with a packed weight block: one problem per workgroup out of LDS (gemm_wgp16_kernels.hip, round 5)
+  // (8-bit FLOAT weights also as whole 64-tiles: 64^3 0.66 -> 0.74; int8 weights with row scales stay with the LDS-B kernel there: 0.70 against 0.68)
+  if ((a.m % 64) || (a.n % 64) || (a.k % 32) || kind != 4) { int taken = 0; const int e = launch_gemm_wgp16_w8(a, kind, st, name, &taken); if (taken) return e; }
+  const dim3 grid = wave_grid(a, big);
+  const int tw = big ? 64 : 32;
+  const bool exact = (a.m % tw) == 0 && (a.n % tw) == 0 && (a.k % 32) == 0 && ((b_bits(a) | (unsigned long long)((long long)a.ldb * 2)) & 15ull) == 0 && strided_forms(a) &&
+    (kind >= 2 || ((a_bits(a) & 1ull) == 0));
+  const bool bl = !exact && !(a.k & 1) && ragged16_b_dwords(a);        // ragged shapes with B on dwords: B through LDS
+  const bool xlds = true;      // whole tiles: B through LDS by 16-byte requests (round 5: adopted, 64^3 bf8 0.605 -> 0.658, scaled i8 0.628 -> 0.659: profiles/r05_ragged16_switches.jsonl)
+  static const kfn kernel[2][5][4] = {      // [2 x 2 tiles][kind][exact B through LDS, exact, ragged B through LDS, masked]
+    {{gemm_w8_bf16_kernel<1, 1, 0, true, true>, gemm_w8_bf16_kernel<1, 1, 0, true>, gemm_w8_bf16_kernel<1, 1, 0, false, true>, gemm_w8_bf16_kernel<1, 1, 0, false>},
+     {gemm_w8_bf16_kernel<1, 1, 1, true, true>, gemm_w8_bf16_kernel<1, 1, 1, true>, gemm_w8_bf16_kernel<1, 1, 1, false, true>, gemm_w8_bf16_kernel<1, 1, 1, false>},
+     {gemm_w8_bf16_kernel<1, 1, 2, true, true>, gemm_w8_bf16_kernel<1, 1, 2, true>, gemm_w8_bf16_kernel<1, 1, 2, false, true>, gemm_w8_bf16_kernel<1, 1, 2, false>},
+     {gemm_w8_bf16_kernel<1, 1, 3, true, true>, gemm_w8_bf16_kernel<1, 1, 3, true>, gemm_w8_bf16_kernel<1, 1, 3, false, true>, gemm_w8_bf16_kernel<1, 1, 3, false>},
+     {gemm_w8_bf16_kernel<1, 1, 4, true, true>, gemm_w8_bf16_kernel<1, 1, 4, true>, gemm_w8_bf16_kernel<1, 1, 4, false, true>, gemm_w8_bf16_kernel<1, 1, 4, false>}},
+    {{gemm_w8_bf16_kernel<2, 2, 0, true, true>, gemm_w8_bf16_kernel<2, 2, 0, true>, gemm_w8_bf16_kernel<2, 2, 0, false, true>, gemm_w8_bf16_kernel<2, 2, 0, false>},
+     {gemm_w8_bf16_kernel<2, 2, 1, true, true>, gemm_w8_bf16_kernel<2, 2, 1, true>, gemm_w8_bf16_kernel<2, 2, 1, false, true>, gemm_w8_bf16_kernel<2, 2, 1, false>},
+     {gemm_w8_bf16_kernel<2, 2, 2, true, true>, gemm_w8_bf16_kernel<2, 2, 2, true>, gemm_w8_bf16_kernel<2, 2, 2, false, true>, gemm_w8_bf16_kernel<2, 2, 2, false>},
+     {gemm_w8_bf16_kernel<2, 2, 3, true, true>, gemm_w8_bf16_kernel<2, 2, 3, true>, gemm_w8_bf16_kernel<2, 2, 3, false, true>, gemm_w8_bf16_kernel<2, 2, 3, false>},
+     {gemm_w8_bf16_kernel<2, 2, 4, true, true>, gemm_w8_bf16_kernel<2, 2, 4, true>, gemm_w8_bf16_kernel<2, 2, 4, false, true>, gemm_w8_bf16_kernel<2, 2, 4, false>}}};
+  launch_tile(kernel[big][kind][exact ? (xlds ? 0 : 1) : (bl ? 2 : 3)], grid, 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// gemm_mfma_f32_kernel: mode = GM_MASKED / GM_EXACT / GM_STAGED
+static void launch_mfma_f32(const GemmArgs& a, bool big, int mode, dim3 grid, hipStream_t st) {
+  static const kfn kernel[2][3][2][2] = {      // [2 x 2 tiles][mode][ta][tb]
+    {{{gemm_mfma_f32_kernel<1, 1, false, false, GM_MASKED>, gemm_mfma_f32_kernel<1, 1, false, true, GM_MASKED>}, {gemm_mfma_f32_kernel<1, 1, true, false, GM_MASKED>, gemm_mfma_f32_kernel<1, 1, true, true, GM_MASKED>}},
+     {{gemm_mfma_f32_kernel<1, 1, false, false, GM_EXACT>, gemm_mfma_f32_kernel<1, 1, false, true, GM_EXACT>}, {gemm_mfma_f32_kernel<1, 1, true, false, GM_EXACT>, gemm_mfma_f32_kernel<1, 1, true, true, GM_EXACT>}},
+     {{gemm_mfma_f32_kernel<1, 1, false, false, GM_STAGED>, gemm_mfma_f32_kernel<1, 1, false, true, GM_STAGED>}, {gemm_mfma_f32_kernel<1, 1, true, false, GM_STAGED>, gemm_mfma_f32_kernel<1, 1, true, true, GM_STAGED>}}},
+    {{{gemm_mfma_f32_kernel<2, 2, false, false, GM_MASKED>, gemm_mfma_f32_kernel<2, 2, false, true, GM_MASKED>}, {gemm_mfma_f32_kernel<2, 2, true, false, GM_MASKED>, gemm_mfma_f32_kernel<2, 2, true, true, GM_MASKED>}},
+     {{gemm_mfma_f32_kernel<2, 2, false, false, GM_EXACT>, gemm_mfma_f32_kernel<2, 2, false, true, GM_EXACT>}, {gemm_mfma_f32_kernel<2, 2, true, false, GM_EXACT>, gemm_mfma_f32_kernel<2, 2, true, true, GM_EXACT>}},
+     {{gemm_mfma_f32_kernel<2, 2, false, false, GM_STAGED>, gemm_mfma_f32_kernel<2, 2, false, true, GM_STAGED>}, {gemm_mfma_f32_kernel<2, 2, true, false, GM_STAGED>, gemm_mfma_f32_kernel<2, 2, true, true, GM_STAGED>}}}};
+  static_assert(GM_MASKED == 0 && GM_EXACT == 1 && GM_STAGED == 2, "the modes index the table");
+  launch_tile(kernel[big][mode][trans_a(a)][trans_b(a)], grid, 256, 0, st, a);
+}
+
+// f32, one 32 x 32 tile per wave
+static int launch_f32_1x1(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  const dim3 grid = wave_grid(a, 32, 32);
+  const bool aligned = pl.exact && operands_aligned16(a, 4);
+  if (aligned && f32_dma_mode() >= 2 && a.lda < (1 << 22) && a.ldb < (1 << 22)) {
+    static const kfn kernel[2][2] = {{gemm_f32_dma_kernel<1, 1, false, false>, gemm_f32_dma_kernel<1, 1, false, true>}, {gemm_f32_dma_kernel<1, 1, true, false>, gemm_f32_dma_kernel<1, 1, true, true>}};      // [ta][tb]
+    *name = "gemm_f32_dma_kernel<1,1>";
+    launch_tile(kernel[trans_a(a)][trans_b(a)], grid, 256, 0, st, a);
+  }
+  else if (aligned && f32_lean_ok(a)) {
+    *name = "gemm_f32_stream_kernel_lean";
+    // cache policy (see the kernel).  Streaming hint of the calling thread (libxsmm_hip_set_streaming_hint): 2 = operands are read once
+    // from HBM -> nt loads; 1 = operands are re-read / cache resident -> never nt; 0 (default) = decide by size: a launch that moves
+    // more than the Infinity Cache holds cannot have resident operands.
+    const bool c16 = (((c_bits(a) | (unsigned long long)((long long)a.ldc * 4)) & 15ull) == 0ull);
+    int pol = stream_nt(a, 4, 4) ? 1 : 0;
+    if (pol == 1 && c16) pol = 3;                        // nt loads AND whole 16-byte stores
+    if ((pol == 0 || pol == 3) && !c16) pol = pol == 0 ? 2 : 1;
+    return launch_gemm_f32_lean(a, pol, st);
+  }
+  else if (aligned && a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22)) {
+    static const kfn kernel[2][2] = {{gemm_f32_stream_kernel<false, false>, gemm_f32_stream_kernel<false, true>}, {gemm_f32_stream_kernel<true, false>, gemm_f32_stream_kernel<true, true>}};      // [ta][tb]
+    *name = "gemm_f32_stream_kernel";
+    launch_tile(kernel[trans_a(a)][trans_b(a)], grid, 256, 0, st, a);
+  }
+  else if (aligned) launch_mfma_f32(a, false, GM_STAGED, grid, st);
+  else if (pl.exact) launch_mfma_f32(a, false, GM_EXACT, grid, st);
+  else if (f32_blob_ok(a)) { *name = "gemm_f32_blob_kernel"; launch_tile(gemm_f32_blob_kernel, grid, 256, 0, st, a); }
+  else launch_mfma_f32(a, false, GM_MASKED, grid, st);
+  return (int)hipGetLastError();
+}
+
+// f32, 2 x 2 tiles of 32 x 32 per wave
+static int launch_f32_2x2(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  dim3 grid = wave_grid(a, 64, 64);
+  const bool aligned = pl.exact && operands_aligned16(a, 4);
+  const bool one64 = pl.exact && a.m == 64 && a.n == 64;
+  if (one64 && a.bs_b == 0 && f32_wg64_ok(a) && aligned) {       // B shared by the batch: persistent workgroups, B's operands in registers
+    int taken = 0;
+    const int e64 = launch_gemm_f32_wg64_sharedb(a, stream_nt(a, 4, 4), st, name, &taken);
+    if (taken) return e64;
+  }
+  if (one64 && f32_wg64_ok(a) && aligned) {
+    a.map2d_shift = 0;                                  // one problem per workgroup: the super-tile dealing counts four problems per workgroup
+    grid = dim3(a.nbatch);
+    static const kfn kernel[2] = {gemm_f32_wg64_kernel<0>, gemm_f32_wg64_kernel<2>};      // [nt]
+    *name = "gemm_f32_wg64_kernel";
+    launch_tile(kernel[stream_nt(a, 4, 4)], grid, 256, 0, st, a);
+  }
+  else if (aligned && f32_dma_mode() >= 1 && a.lda < (1 << 22) && a.ldb < (1 << 22)) {
+    static const kfn kernel[2][2] = {{gemm_f32_dma_kernel<2, 2, false, false>, gemm_f32_dma_kernel<2, 2, false, true>}, {gemm_f32_dma_kernel<2, 2, true, false>, gemm_f32_dma_kernel<2, 2, true, true>}};      // [ta][tb]
+    const int ta = trans_a(a), tb = trans_b(a);
+    *name = "gemm_f32_dma_kernel<2,2>";
+    launch_tile(!ta && !tb && stream_nt(a, 4, 4) ? gemm_f32_dma_kernel<2, 2, false, false, 2> : kernel[ta][tb], grid, 256, 0, st, a);      // (the nt form exists for NN only)
+  }
+  else if (aligned) launch_mfma_f32(a, true, GM_STAGED, grid, st);
+  else if (pl.exact) launch_mfma_f32(a, true, GM_EXACT, grid, st);
+  else launch_mfma_f32(a, true, GM_MASKED, grid, st);
+  return (int)hipGetLastError();
+}
+
+// bf16 and IEEE halves, VNNI-2 A and flat B: P_BF16_1x1 (one 32 x 32 tile per wave) and P_BF16_2x2
+static int launch_16bit(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  const bool big = pl.path == P_BF16_2x2, f16 = a.a_type == LIBXSMM_DATATYPE_F16;
   // IEEE halves take the bf16 fast paths with f32 accumulation and f16 or f32 C (round 6: any beta and the fused operators too -- the start value is rounded to f16 on
   // its way into the accumulators, tile_init<.., F16S>)
-  const bool f16_fast = a.a_type == LIBXSMM_DATATYPE_F16 && a.b_type == LIBXSMM_DATATYPE_F16 && !a.comp_f16 && !a.vnni_c &&
-    (a.c_type == LIBXSMM_DATATYPE_F16 || a.c_type == LIBXSMM_DATATYPE_F32);
-  // 8-bit operands on the masked matrix-core kernel: any shape with whole k-quads, any alignment, any batch-reduce form.  Returns false for what it does not
-  // take (more than 2^31 bytes inside one operand).
-  auto launch_m8 = [&](bool big) -> bool {
-    constexpr int tile_env = 0;      // experiments: 1 forces 32 x 32 tiles, 2 forces 64 x 64
-    if (tile_env == 1) big = false; else if (tile_env == 2) big = true;
-    const bool fp8 = a.a_type == LIBXSMM_DATATYPE_BF8 || a.a_type == LIBXSMM_DATATYPE_HF8;
-    if (fp8 && a.c_type != LIBXSMM_DATATYPE_F32 && a.vnni_c) return false;
-    if ((a.k & 3) || a.k <= 0) return false;
-    const bool ua = a.a_type == LIBXSMM_DATATYPE_U8, ub = a.b_type == LIBXSMM_DATATYPE_U8;
-    // packed operand blocks of several tiles: one problem per workgroup, whole problem in LDS (gemm_wgp8_kernels.hip, round 5); an error of that launch is left
-    // for the hipGetLastError() behind the switch
-    { int taken = 0; (void)launch_gemm_wgp8(a, fp8 ? (a.a_type == LIBXSMM_DATATYPE_HF8 ? 2 : 1) : 0, ua, ub, stream, kernel_name, &taken); if (taken) return true; }
-    grid = big ? wave_grid(64, 64) : wave_grid(32, 32);
-    if (kernel_name) *kernel_name = big ? "gemm_mfma_8bit_kernel<2,2>" : "gemm_mfma_8bit_kernel<1,1>";
-    // strided forms whose blocks, rows and columns start on dwords: B through LDS (see the kernel); LIBXSMM_HIP_M8_LDS=0 keeps B in registers (measurement switch)
-    constexpr bool lds_off = false;
-    const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a | (unsigned long long)a.bs_b |
-      (unsigned long long)(a.br_mode == 3 ? (a.br_stride_a | a.br_stride_b) : 0) | (unsigned long long)a.ldb;
-    const bool bl = !lds_off && !a.list_a && a.br_mode != 1 && a.br_mode != 2 && (abits & 3ull) == 0ull &&
-      (unsigned long long)a.n * (unsigned long long)a.ldb < (1ull << 31) && (unsigned long long)a.k * (unsigned long long)a.lda < (1ull << 31);
-#define LAUNCH_M8K_(MT_, NT_, K_, UA_, UB_) do { if (bl) hipLaunchKernelGGL((gemm_mfma_8bit_kernel<MT_, NT_, K_, UA_, UB_, true>), grid, dim3(256), 0, st, a); \
-                                                 else hipLaunchKernelGGL((gemm_mfma_8bit_kernel<MT_, NT_, K_, UA_, UB_, false>), grid, dim3(256), 0, st, a); } while (0)
-#define LAUNCH_M8_(MT_, NT_) do { \
-      if (fp8) { if (a.a_type == LIBXSMM_DATATYPE_HF8) LAUNCH_M8K_(MT_, NT_, 2, false, false); else LAUNCH_M8K_(MT_, NT_, 1, false, false); } \
-      else if (!ua && !ub) LAUNCH_M8K_(MT_, NT_, 0, false, false); \
-      else if (ua && !ub) LAUNCH_M8K_(MT_, NT_, 0, true, false); \
-      else if (!ua && ub) LAUNCH_M8K_(MT_, NT_, 0, false, true); \
-      else LAUNCH_M8K_(MT_, NT_, 0, true, true); } while (0)
-    if (big) LAUNCH_M8_(2, 2); else LAUNCH_M8_(1, 1);
-#undef LAUNCH_M8_
-#undef LAUNCH_M8K_
-    return true;
-  };
-  switch (pl.path) {
-    case P_W8_1x1: case P_W8_2x2: {
-      const bool big = pl.path == P_W8_2x2, va8 = (a.flags & LIBXSMM_GEMM_FLAG_VNNI_A) != 0;
-      const int kind = a.a_type == LIBXSMM_DATATYPE_I8 ? 4 : ((a.a_type == LIBXSMM_DATATYPE_HF8 ? 1 : 0) + (va8 ? 0 : 2));
-      // ragged / several-tile shapes with a packed weight block: one problem per workgroup out of LDS (gemm_wgp16_kernels.hip, round 5)
-      // (8-bit FLOAT weights also as whole 64-tiles: 64^3 0.66 -> 0.74; int8 weights with row scales stay with the LDS-B kernel there: 0.70 against 0.68)
-      if ((a.m % 64) || (a.n % 64) || (a.k % 32) || kind != 4) { int taken = 0; const int e = launch_gemm_wgp16_w8(a, kind, stream, kernel_name, &taken); if (taken) return e; }
-      grid = big ? wave_grid(64, 64) : wave_grid(32, 32);
-      const int tw = big ? 64 : 32;
-      const unsigned long long bbits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0) | (unsigned long long)((long long)a.ldb * 2);
-      const bool exact = (a.m % tw) == 0 && (a.n % tw) == 0 && (a.k % 32) == 0 && (bbits & 15ull) == 0 && !a.list_a && a.br_mode != 1 && a.br_mode != 2 &&
-        (kind >= 2 || ((((unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | (unsigned long long)(a.br_mode == 3 ? a.br_stride_a : 0)) & 1ull) == 0));
-      const bool bl = !exact && !(a.k & 1) && ragged16_b_dwords(a);        // ragged shapes with B on dwords: B through LDS
-      const bool xlds = true;      // whole tiles: B through LDS by 16-byte requests (round 5: adopted, 64^3 bf8 0.605 -> 0.658, scaled i8 0.628 -> 0.659: profiles/r05_ragged16_switches.jsonl)
-#define LAUNCH_W8K_(MT_, NT_, K_) do { if (exact && xlds) hipLaunchKernelGGL((gemm_w8_bf16_kernel<MT_, NT_, K_, true, true>), grid, dim3(256), 0, st, a); \
-                                       else if (exact) hipLaunchKernelGGL((gemm_w8_bf16_kernel<MT_, NT_, K_, true>), grid, dim3(256), 0, st, a); \
-                                       else if (bl) hipLaunchKernelGGL((gemm_w8_bf16_kernel<MT_, NT_, K_, false, true>), grid, dim3(256), 0, st, a); \
-                                       else hipLaunchKernelGGL((gemm_w8_bf16_kernel<MT_, NT_, K_, false>), grid, dim3(256), 0, st, a); } while (0)
-#define LAUNCH_W8_(MT_, NT_) do { switch (kind) { case 0: LAUNCH_W8K_(MT_, NT_, 0); break; case 1: LAUNCH_W8K_(MT_, NT_, 1); break; case 2: LAUNCH_W8K_(MT_, NT_, 2); break; \
-                                                  case 3: LAUNCH_W8K_(MT_, NT_, 3); break; default: LAUNCH_W8K_(MT_, NT_, 4); break; } } while (0)
-      if (big) LAUNCH_W8_(2, 2); else LAUNCH_W8_(1, 1);
-#undef LAUNCH_W8_
-#undef LAUNCH_W8K_
-      break;
-    }
-    case P_M8_1x1: case P_M8_2x2: {
-      if (launch_m8(pl.path == P_M8_2x2)) break;
-      if (kernel_name) *kernel_name = "gemm_generic_kernel";
-      const long long gblocks = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
-      hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)gblocks), dim3(64, 4), 0, st, a);
-      break;
-    }
-    case P_F32_T16: grid = wave_grid(16, 16); hipLaunchKernelGGL(gemm_mfma_f32_t16_kernel, grid, dim3(256), 0, st, a); break;
-    case P_F32_1x1:
-      grid = wave_grid(32, 32);
-      if (pl.exact && operands_aligned16(a, 4) && f32_dma_mode() >= 2 && a.lda < (1 << 22) && a.ldb < (1 << 22)) {
-        const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B;
-        if (kernel_name) *kernel_name = "gemm_f32_dma_kernel<1,1>";
-        if (!ta && !tb) hipLaunchKernelGGL((gemm_f32_dma_kernel<1, 1, false, false>), grid, dim3(256), 0, st, a);
-        else if (ta && !tb) hipLaunchKernelGGL((gemm_f32_dma_kernel<1, 1, true, false>), grid, dim3(256), 0, st, a);
-        else if (!ta && tb) hipLaunchKernelGGL((gemm_f32_dma_kernel<1, 1, false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_f32_dma_kernel<1, 1, true, true>), grid, dim3(256), 0, st, a);
-      }
-      else if (pl.exact && operands_aligned16(a, 4) && f32_lean_ok(a)) {
-        if (kernel_name) *kernel_name = "gemm_f32_stream_kernel_lean";
-        // cache policy (see the kernel).  Streaming hint of the calling thread (libxsmm_hip_set_streaming_hint): 2 = operands are read once
-        // from HBM -> nt loads; 1 = operands are re-read / cache resident -> never nt; 0 (default) = decide by size: a launch that moves
-        // more than the Infinity Cache holds cannot have resident operands.
-        const bool c16 = ((((unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c | (unsigned long long)((long long)a.ldc * 4)) & 15ull) == 0ull);
-        int pol = stream_nt(a, 4, 4) ? 1 : 0;
-        if (pol == 1 && c16) pol = 3;                        // nt loads AND whole 16-byte stores
-        if ((pol == 0 || pol == 3) && !c16) pol = pol == 0 ? 2 : 1;
-        return launch_gemm_f32_lean(a, pol, stream);
-      }
-      else if (pl.exact && operands_aligned16(a, 4) && a.lda < (1 << 22) && a.ldb < (1 << 22) && a.ldc < (1 << 22)) {
-        const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B;
-        if (kernel_name) *kernel_name = "gemm_f32_stream_kernel";
-        if (!ta && !tb) hipLaunchKernelGGL((gemm_f32_stream_kernel<false, false>), grid, dim3(256), 0, st, a);
-        else if (ta && !tb) hipLaunchKernelGGL((gemm_f32_stream_kernel<true, false>), grid, dim3(256), 0, st, a);
-        else if (!ta && tb) hipLaunchKernelGGL((gemm_f32_stream_kernel<false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_f32_stream_kernel<true, true>), grid, dim3(256), 0, st, a);
-      }
-      else if (pl.exact && operands_aligned16(a, 4)) launch_f32<1, 1, GM_STAGED>(a, grid, st);
-      else if (pl.exact) launch_f32<1, 1, GM_EXACT>(a, grid, st);
-      else if (f32_blob_ok(a)) { if (kernel_name) *kernel_name = "gemm_f32_blob_kernel"; hipLaunchKernelGGL(gemm_f32_blob_kernel, grid, dim3(256), 0, st, a); }
-      else launch_f32<1, 1, GM_MASKED>(a, grid, st);
-      break;
-    case P_F32_2x2:
-      grid = wave_grid(64, 64);
-      if (pl.exact && a.m == 64 && a.n == 64 && a.bs_b == 0 && f32_wg64_ok(a) && operands_aligned16(a, 4)) {       // B shared by the batch: persistent workgroups, B's operands in registers
-        int taken = 0;
-        const int e64 = launch_gemm_f32_wg64_sharedb(a, stream_nt(a, 4, 4), stream, kernel_name, &taken);
-        if (taken) return e64;
-      }
-      if (pl.exact && a.m == 64 && a.n == 64 && f32_wg64_ok(a) && operands_aligned16(a, 4)) {
-        a.map2d_shift = 0;                                  // one problem per workgroup: the super-tile dealing counts four problems per workgroup
-        grid = dim3(a.nbatch);
-        if (kernel_name) *kernel_name = "gemm_f32_wg64_kernel";
-        if (stream_nt(a, 4, 4)) hipLaunchKernelGGL((gemm_f32_wg64_kernel<2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_f32_wg64_kernel<0>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (pl.exact && operands_aligned16(a, 4) && f32_dma_mode() >= 1 && a.lda < (1 << 22) && a.ldb < (1 << 22)) {
-        const bool ta = a.flags & LIBXSMM_GEMM_FLAG_TRANS_A, tb = a.flags & LIBXSMM_GEMM_FLAG_TRANS_B;
-        if (kernel_name) *kernel_name = "gemm_f32_dma_kernel<2,2>";
-        if (!ta && !tb && stream_nt(a, 4, 4)) hipLaunchKernelGGL((gemm_f32_dma_kernel<2, 2, false, false, 2>), grid, dim3(256), 0, st, a);
-        else if (!ta && !tb) hipLaunchKernelGGL((gemm_f32_dma_kernel<2, 2, false, false>), grid, dim3(256), 0, st, a);
-        else if (ta && !tb) hipLaunchKernelGGL((gemm_f32_dma_kernel<2, 2, true, false>), grid, dim3(256), 0, st, a);
-        else if (!ta && tb) hipLaunchKernelGGL((gemm_f32_dma_kernel<2, 2, false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_f32_dma_kernel<2, 2, true, true>), grid, dim3(256), 0, st, a);
-      }
-      else if (pl.exact && operands_aligned16(a, 4)) launch_f32<2, 2, GM_STAGED>(a, grid, st);
-      else if (pl.exact) launch_f32<2, 2, GM_EXACT>(a, grid, st);
-      else launch_f32<2, 2, GM_MASKED>(a, grid, st);
-      break;
-    case P_BF16_1x1:
-      // gemm_wgp.hpp (round 5): ragged shapes, and whole 32-tiles that are several tiles per problem (96^3 as nine waves that each fetched their own panels: 0.39)
-      { int taken = 0; const int e = launch_gemm_wgp16(a, stream, kernel_name, &taken); if (taken) return e; }
-      grid = wave_grid(32, 32);
-      if (a.a_type == LIBXSMM_DATATYPE_F16 && f16_fast && pl.exact && bf16_stream_ok(a)) {       // the bf16 streaming kernel on IEEE halves
-        if (kernel_name) *kernel_name = "gemm_f16_stream_kernel<1,1>";
-        if (stream_nt(a, 2, typesize_c(a))) hipLaunchKernelGGL((gemm_bf16_stream_kernel<1, 1, 2, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_bf16_stream_kernel<1, 1, 0, true>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (a.a_type == LIBXSMM_DATATYPE_F16) {
-        if (kernel_name) *kernel_name = "gemm_mfma_f16_kernel<1,1>";
-        if (pl.exact) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, true, true>), grid, dim3(256), 0, st, a);
-        else if (ragged16_b_dwords(a) && ragged16_bounded(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, false, true, true, true>), grid, dim3(256), 0, st, a);
-        else if (ragged16_b_dwords(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, false, true, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, false, true>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (pl.exact && bf16_stream_ok(a)) {
-        if (kernel_name) *kernel_name = "gemm_bf16_stream_kernel<1,1>";
-        if (stream_nt(a, 2, typesize_c(a))) hipLaunchKernelGGL((gemm_bf16_stream_kernel<1, 1, 2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_bf16_stream_kernel<1, 1, 0>), grid, dim3(256), 0, st, a);
-      }
-      else if (pl.exact) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, true>), grid, dim3(256), 0, st, a);
-      else if (ragged16_b_dwords(a) && ragged16_bounded(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, false, false, true, true>), grid, dim3(256), 0, st, a);
-      else if (ragged16_b_dwords(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, false, false, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gemm_mfma_bf16_kernel<1, 1, false>), grid, dim3(256), 0, st, a);
-      break;
-    case P_BF16_2x2:
-      // (whole 64-tiles stay with the 64^3-per-workgroup kernel: 0.735 against 0.753 at 65 536 problems but 0.61 against 0.53 at 4096, profiles/r05_wgp_pair.jsonl)
-      if (!pl.exact) { int taken = 0; const int e = launch_gemm_wgp16(a, stream, kernel_name, &taken); if (taken) return e; }       // gemm_wgp.hpp (round 5)
-      grid = wave_grid(64, 64);
-      if (pl.exact && a.m == 64 && a.n == 64 && !a.batch_inner && (a.a_type != LIBXSMM_DATATYPE_F16 || f16_fast)) {       // gemm_w64_kernels.hip (round 6): 64^3, one problem per wave
-        int taken = 0; const int e = launch_gemm_16bit_w64(a, stream_nt(a, 2, typesize_c(a)), stream, kernel_name, &taken); if (taken) return e;
-      }
-      if (a.a_type == LIBXSMM_DATATYPE_F16 && f16_fast && pl.exact && a.m == 64 && a.n == 64 && !a.batch_inner && bf16_wg64_ok(a)) {
-        a.map2d_shift = 0;
-        grid = dim3(a.nbatch);
-        if (kernel_name) *kernel_name = "gemm_f16_wg64_kernel";
-        hipLaunchKernelGGL((gemm_bf16_wg64_kernel<0, true>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (a.a_type == LIBXSMM_DATATYPE_F16 && f16_fast && pl.exact && bf16_stream_ok(a)) {
-        if (kernel_name) *kernel_name = "gemm_f16_stream_kernel<2,2>";
-        hipLaunchKernelGGL((gemm_bf16_stream_kernel<2, 2, 0, true>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (a.a_type == LIBXSMM_DATATYPE_F16) {
-        if (kernel_name) *kernel_name = "gemm_mfma_f16_kernel<2,2>";
-        if (pl.exact) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, true, true>), grid, dim3(256), 0, st, a);
-        else if (ragged16_b_dwords(a) && ragged16_bounded(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, false, true, true, true>), grid, dim3(256), 0, st, a);
-        else if (ragged16_b_dwords(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, false, true, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, false, true>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (pl.exact && a.m == 64 && a.n == 64 && !a.batch_inner && bf16_wg64_ok(a)) {
-        a.map2d_shift = 0;
-        grid = dim3(a.nbatch);
-        if (kernel_name) *kernel_name = "gemm_bf16_wg64_kernel";
-        // cacheable loads whatever the size: non-temporal loads measured slower on this kernel (batch 65536 from HBM: 0.71 vs 0.75; batch 4096: 0.59 vs 0.61)
-        hipLaunchKernelGGL((gemm_bf16_wg64_kernel<0>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (pl.exact && bf16_stream_ok(a)) {
-        if (kernel_name) *kernel_name = "gemm_bf16_stream_kernel<2,2>";
-        // measured (batch 65536, operands from HBM): nt on the B stream takes the 32^3 kernel from 0.72 to 0.84 of the HBM roofline but the
-        // 64^3 kernel from 0.68 to 0.60 -- so only the <1,1> form asks for it
-        hipLaunchKernelGGL((gemm_bf16_stream_kernel<2, 2, 0>), grid, dim3(256), 0, st, a);
-      }
-      else if (pl.exact) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, true>), grid, dim3(256), 0, st, a);
-      else if (ragged16_b_dwords(a) && ragged16_bounded(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, false, false, true, true>), grid, dim3(256), 0, st, a);
-      else if (ragged16_b_dwords(a)) hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, false, false, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gemm_mfma_bf16_kernel<2, 2, false>), grid, dim3(256), 0, st, a);
-      break;
-    case P_MXMX_1x1: case P_MXMX_2x2: {
-      // operands are read as dwords, scales as bytes: any alignment of the leading dimensions works; bases dword aligned; offsets < 4 GiB
-      const unsigned long long bits = (unsigned long long)(size_t)a.a | (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_a | (unsigned long long)a.bs_b |
-        (unsigned long long)(a.br_mode == 3 ? (a.br_stride_a | a.br_stride_b) : 0);
-      const bool ok = !a.list_a && (bits & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.k < (1ll << 31);
-      if (ok) {
-        if (a.a_type == LIBXSMM_DATATYPE_MXHF6) {           // E2M3 on the matrix cores (the plan sends E3M2 to the exact kernel, see plan_gemm)
-          constexpr bool small6 = false;
-          const bool big6 = pl.path == P_MXMX_2x2 && !small6;
-          const long long lim = (1ll << 31) / 3;
-          if ((long long)a.lda * (a.k / 4) < lim && (long long)a.ldb * (a.k / 4) < lim) {
-            constexpr int gather6 = 0;
-            a.tune = gather6;
-            grid = big6 ? wave_grid(64, 64) : wave_grid(32, 32);
-            if (kernel_name) *kernel_name = big6 ? "gemm_mx6_stream_kernel<2,2>" : "gemm_mx6_stream_kernel<1,1>";
-            if (big6) hipLaunchKernelGGL((gemm_mx_stream_kernel<2, 2, 2>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((gemm_mx_stream_kernel<1, 1, 2>), grid, dim3(256), 0, st, a);
-            break;
-          }
-          if (kernel_name) *kernel_name = "gemm_generic_kernel";
-          const long long gb6 = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
-          hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)gb6), dim3(64, 4), 0, st, a);
-          break;
-        }
-        const int fmt = a.a_type == LIBXSMM_DATATYPE_MXFP4X2 ? 4 : (a.a_type == LIBXSMM_DATATYPE_MXBF8 ? 1 : 0);
-        const bool big = pl.path == P_MXMX_2x2;
-        grid = big ? wave_grid(64, 64) : wave_grid(32, 32);
-#define LAUNCH_MX_(MT_, NT_) do { \
-          if (fmt == 4) hipLaunchKernelGGL((gemm_mx_stream_kernel<MT_, NT_, 4>), grid, dim3(256), 0, st, a); \
-          else if (fmt == 1) hipLaunchKernelGGL((gemm_mx_stream_kernel<MT_, NT_, 1>), grid, dim3(256), 0, st, a); \
-          else hipLaunchKernelGGL((gemm_mx_stream_kernel<MT_, NT_, 0>), grid, dim3(256), 0, st, a); } while (0)
-        if (big) LAUNCH_MX_(2, 2); else LAUNCH_MX_(1, 1);
-#undef LAUNCH_MX_
-        break;
-      }
-      if (kernel_name) *kernel_name = "gemm_generic_kernel";
-      const long long gblocks = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
-      hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)gblocks), dim3(64, 4), 0, st, a);
-      break;
-    }
-    case P_MX4_1x1: case P_MX4_2x2: {
-      // B columns 16-byte aligned (LDS-DMA); A and the scales are read byte-wise (any alignment); offsets inside a tile < 4 GiB
-      const unsigned long long bits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0) | (unsigned long long)((long long)a.ldb * 2);
-      const bool ok = !a.list_a && a.br_mode != 1 && a.br_mode != 2 && (bits & 15ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n * 2 < (1ll << 31);
-      if (ok) {
-        if (pl.path == P_MX4_2x2) { grid = wave_grid(64, 64); hipLaunchKernelGGL((gemm_mxfp4_stream_kernel<2, 2>), grid, dim3(256), 0, st, a); }
-        else { grid = wave_grid(32, 32); hipLaunchKernelGGL((gemm_mxfp4_stream_kernel<1, 1>), grid, dim3(256), 0, st, a); }
-        break;
-      }
-      if (kernel_name) *kernel_name = "gemm_generic_kernel";
-      const long long gblocks = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
-      hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)gblocks), dim3(64, 4), 0, st, a);
-      break;
-    }
-    case P_FP8_1x1: case P_FP8_2x2: {
-      const unsigned long long bits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0) | (unsigned long long)a.ldb;
-      const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | (unsigned long long)(a.br_mode == 3 ? a.br_stride_a : 0);
-      const bool ok = !a.list_a && a.br_mode != 1 && a.br_mode != 2 && (bits & 15ull) == 0 && (abits & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n < (1ll << 31);
-      if (ok) {
-        const bool hf8 = a.a_type == LIBXSMM_DATATYPE_HF8, big = pl.path == P_FP8_2x2;
-        // whole 32-tiles, several per problem (96^3: nine): one problem per workgroup out of LDS instead of nine waves that each fetch their own panels (gemm_wgp8_kernels.hip)
-        // (also whole 64-tiles -- 64^3 was one wave per problem: bf8 0.64 -> 0.76, i8 0.65 -> 0.75, profiles/r05_wgp_pair.jsonl; more than twelve tiles are not taken there)
-        if (a.m > 32 && a.n > 32 && (a.m / 32) * (a.n / 32) <= 12) { int taken = 0; (void)launch_gemm_wgp8(a, hf8 ? 2 : 1, false, false, stream, kernel_name, &taken); if (taken) break; }      // (128^3: 0.66 here against 0.43 there)
-        grid = big ? wave_grid(64, 64) : wave_grid(32, 32);
-        if (a.c_type != LIBXSMM_DATATYPE_F32) {            // C in the operands' type
-          if (a.vnni_c) goto fp8_generic;
-          if (kernel_name) *kernel_name = big ? "gemm_fp8c8_stream_kernel<2,2>" : "gemm_fp8c8_stream_kernel<1,1>";
-          if (big) { if (hf8) hipLaunchKernelGGL((gemm_fp8_stream_kernel<2, 2, true, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_fp8_stream_kernel<2, 2, false, true>), grid, dim3(256), 0, st, a); }
-          else { if (hf8) hipLaunchKernelGGL((gemm_fp8_stream_kernel<1, 1, true, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_fp8_stream_kernel<1, 1, false, true>), grid, dim3(256), 0, st, a); }
-          break;
-        }
-        if (big) { if (hf8) hipLaunchKernelGGL((gemm_fp8_stream_kernel<2, 2, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_fp8_stream_kernel<2, 2, false>), grid, dim3(256), 0, st, a); }
-        else { if (hf8) hipLaunchKernelGGL((gemm_fp8_stream_kernel<1, 1, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_fp8_stream_kernel<1, 1, false>), grid, dim3(256), 0, st, a); }
-        break;
-      }
-      fp8_generic:
-      if (launch_m8(pl.path == P_FP8_2x2)) break;            // unaligned operands, pointer / offset lists: the masked matrix-core kernel
-      if (kernel_name) *kernel_name = "gemm_generic_kernel";
-      const long long gblocks = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
-      hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)gblocks), dim3(64, 4), 0, st, a);
-      break;
-    }
-    case P_MX4I8_1x1: case P_MX4I8_2x2: {
-      const unsigned long long bits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0) | (unsigned long long)a.ldb;
-      const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | (unsigned long long)(a.br_mode == 3 ? a.br_stride_a : 0) |
-        (unsigned long long)(size_t)a.b_scf | (unsigned long long)a.bs_bscf;
-      const bool ok = !a.list_a && a.br_mode != 1 && a.br_mode != 2 && (bits & 15ull) == 0 && (abits & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n < (1ll << 31) &&
-        (a.c_type == LIBXSMM_DATATYPE_F32 || a.c_type == LIBXSMM_DATATYPE_BF16) && a.a_scf && a.b_scf;
-      if (ok) {
-        // waves that walk several consecutive tiles with the next chunk's operands in flight: at least 8 K waves per launch, at most 8 tiles each
-        constexpr int pipe = 8;
-        a.tiles_m = a.m / 32; a.tiles_n = a.n / 32; a.map2d_shift = 0;
-        const unsigned long long tiles = (unsigned long long)a.tiles_m * a.tiles_n * a.nbatch;
-        const bool c_ok = (a.flags & LIBXSMM_GEMM_FLAG_BETA_0) == 0 || ((((unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c | (unsigned long long)a.bs_c2) & 15ull) == 0 &&
-          ((unsigned long long)a.ldc * (a.c_type == LIBXSMM_DATATYPE_F32 ? 4ull : 2ull)) % 16ull == 0 && !a.list_c);
-        if (pipe > 0 && c_ok && tiles < (1ull << 31) && (a.k >> 6) * a.br_count < (1ull << 31)) {
-          const unsigned int per_wave = (unsigned int)std::min<unsigned long long>((unsigned long long)pipe, std::max<unsigned long long>(1ull, tiles / 8192ull));
-          const unsigned long long waves = (tiles + per_wave - 1) / per_wave;
-          // two chunks in flight per wave at three waves per SIMD; four / six at two waves per SIMD measured the same or worse (the kernel is bound by its
-          // ~300 vector instructions per tile -- code expansion, convert / scale / add of 2 x 16 block sums -- not by the operand round trip any more)
-          hipLaunchKernelGGL((gemm_mx4i8_pipe_kernel<2>), dim3((unsigned int)((waves + 3) / 4)), dim3(256), 0, st, a, per_wave, (unsigned int)tiles);
-          if (kernel_name) *kernel_name = "gemm_mx4i8_pipe_kernel";
-          break;
-        }
-        grid = wave_grid(32, 32);
-        hipLaunchKernelGGL((gemm_mx4i8_stream_kernel<1, 1>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      if (kernel_name) *kernel_name = "gemm_generic_kernel";
-      const long long gblocks2 = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
-      hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)gblocks2), dim3(64, 4), 0, st, a);
-      break;
-    }
-    case P_I8_1x1: case P_I8_2x2: {
-      // same alignment contract as the bf16 streaming kernel (element size 1): B columns 16-byte aligned, A dword aligned
-      const unsigned long long bits = (unsigned long long)(size_t)a.b | (unsigned long long)a.bs_b | (unsigned long long)(a.br_mode == 3 ? a.br_stride_b : 0) | (unsigned long long)a.ldb;
-      const unsigned long long abits = (unsigned long long)(size_t)a.a | (unsigned long long)a.bs_a | (unsigned long long)(a.br_mode == 3 ? a.br_stride_a : 0) | (unsigned long long)(size_t)a.c | (unsigned long long)a.bs_c;
-      const bool ok = !a.list_a && a.br_mode != 1 && a.br_mode != 2 && (bits & 15ull) == 0 && (abits & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n < (1ll << 31);
-      const bool i4 = a.a_type == LIBXSMM_DATATYPE_I4X2 || a.a_type == LIBXSMM_DATATYPE_U4X2;
-      if (ok && i4) {
-        const bool big = pl.path == P_I8_2x2;
-        grid = big ? wave_grid(64, 64) : wave_grid(32, 32);
-        if (kernel_name) *kernel_name = big ? "gemm_i4_stream_kernel<2,2>" : "gemm_i4_stream_kernel<1,1>";
-        if (big) hipLaunchKernelGGL((gemm_i8_stream_kernel<2, 2, false, true, 1>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_i8_stream_kernel<1, 1, false, true, 1>), grid, dim3(256), 0, st, a);
-        break;
-      }
-      const int lowbit = a.a_type == LIBXSMM_DATATYPE_I2X4 ? 2 : (a.a_type == LIBXSMM_DATATYPE_I1X8 ? 3 : 0);
-      if (ok && lowbit) {
-        const bool ub = a.b_type == LIBXSMM_DATATYPE_U8, big = pl.path == P_I8_2x2;
-        grid = big ? wave_grid(64, 64) : wave_grid(32, 32);
-        if (kernel_name) *kernel_name = lowbit == 2 ? (big ? "gemm_i2_stream_kernel<2,2>" : "gemm_i2_stream_kernel<1,1>") : (big ? "gemm_i1_stream_kernel<2,2>" : "gemm_i1_stream_kernel<1,1>");
-#define LAUNCH_LB_(MT_, NT_) do { \
-          if (lowbit == 2) { if (ub) hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, false, true, 2>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, false, false, 2>), grid, dim3(256), 0, st, a); } \
-          else { if (ub) hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, false, true, 3>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, false, false, 3>), grid, dim3(256), 0, st, a); } } while (0)
-        if (big) LAUNCH_LB_(2, 2); else LAUNCH_LB_(1, 1);
-#undef LAUNCH_LB_
-        break;
-      }
-      if (ok && !i4 && !lowbit) {
-        const bool ua = a.a_type == LIBXSMM_DATATYPE_U8, ub = a.b_type == LIBXSMM_DATATYPE_U8, big = pl.path == P_I8_2x2;
-        if (a.m > 32 && a.n > 32 && (a.m / 32) * (a.n / 32) <= 12) { int taken = 0; (void)launch_gemm_wgp8(a, 0, ua, ub, stream, kernel_name, &taken); if (taken) break; }      // (as for the 8-bit floats above)
-        grid = big ? wave_grid(64, 64) : wave_grid(32, 32);
-#define LAUNCH_I8_(MT_, NT_) do { \
-          if (!ua && !ub) hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, false, false>), grid, dim3(256), 0, st, a); \
-          else if (ua && !ub) hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, true, false>), grid, dim3(256), 0, st, a); \
-          else if (!ua && ub) hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, false, true>), grid, dim3(256), 0, st, a); \
-          else hipLaunchKernelGGL((gemm_i8_stream_kernel<MT_, NT_, true, true>), grid, dim3(256), 0, st, a); } while (0)
-        if (big) LAUNCH_I8_(2, 2); else LAUNCH_I8_(1, 1);
-#undef LAUNCH_I8_
-        break;
-      }
-      if (!i4 && !lowbit && launch_m8(pl.path == P_I8_2x2)) break;       // unaligned operands, pointer / offset lists: the masked matrix-core kernel
-      if (kernel_name) *kernel_name = "gemm_generic_kernel";
-    }
-    // fallthrough
-    default: {
-      const long long blocks = (long long)((a.m + 63) / 64) * ((a.n + 3) / 4) * (long long)a.nbatch;
-      hipLaunchKernelGGL(gemm_generic_kernel, dim3((unsigned int)blocks), dim3(64, 4), 0, st, a);
-    }
+  const bool f16_fast = f16 && a.b_type == LIBXSMM_DATATYPE_F16 && !a.comp_f16 && !a.vnni_c && (a.c_type == LIBXSMM_DATATYPE_F16 || a.c_type == LIBXSMM_DATATYPE_F32);
+  const bool fast = !f16 || f16_fast;
+  // gemm_wgp.hpp (round 5): ragged shapes, and whole 32-tiles that are several tiles per problem (96^3 as nine waves that each fetched their own panels: 0.39)
+  // (whole 64-tiles stay with the 64^3-per-workgroup kernel: 0.735 against 0.753 at 65 536 problems but 0.61 against 0.53 at 4096, profiles/r05_wgp_pair.jsonl)
+  if (!big || !pl.exact) { int taken = 0; const int e = launch_gemm_wgp16(a, st, name, &taken); if (taken) return e; }
+  dim3 grid = wave_grid(a, big);
+  const bool one64 = big && fast && pl.exact && a.m == 64 && a.n == 64 && !a.batch_inner;
+  if (one64) {       // gemm_w64_kernels.hip (round 6): 64^3, one problem per wave
+    int taken = 0; const int e = launch_gemm_16bit_w64(a, stream_nt(a, 2, typesize_c(a)), st, name, &taken); if (taken) return e;
+  }
+  if (one64 && bf16_wg64_ok(a)) {
+    a.map2d_shift = 0;
+    grid = dim3(a.nbatch);
+    // cacheable loads whatever the size: non-temporal loads measured slower on this kernel (batch 65536 from HBM: 0.71 vs 0.75; batch 4096: 0.59 vs 0.61)
+    static const kfn kernel[2] = {gemm_bf16_wg64_kernel<0>, gemm_bf16_wg64_kernel<0, true>};      // [f16]
+    *name = f16 ? "gemm_f16_wg64_kernel" : "gemm_bf16_wg64_kernel";
+    launch_tile(kernel[f16], grid, 256, 0, st, a);
+  }
+  else if (fast && pl.exact && bf16_stream_ok(a)) {
+    // measured (batch 65536, operands from HBM): nt on the B stream takes the 32^3 kernel from 0.72 to 0.84 of the HBM roofline but the
+    // 64^3 kernel from 0.68 to 0.60 -- so only the <1,1> form asks for it
+    static const kfn kernel[2][3] = {{gemm_bf16_stream_kernel<1, 1, 0>, gemm_bf16_stream_kernel<1, 1, 2>, gemm_bf16_stream_kernel<2, 2, 0>},      // [f16][<1,1>, <1,1> nt, <2,2>]
+                                     {gemm_bf16_stream_kernel<1, 1, 0, true>, gemm_bf16_stream_kernel<1, 1, 2, true>, gemm_bf16_stream_kernel<2, 2, 0, true>}};
+    *name = f16 ? (big ? "gemm_f16_stream_kernel<2,2>" : "gemm_f16_stream_kernel<1,1>") : (big ? "gemm_bf16_stream_kernel<2,2>" : "gemm_bf16_stream_kernel<1,1>");
+    launch_tile(kernel[f16][big ? 2 : (stream_nt(a, 2, typesize_c(a)) ? 1 : 0)], grid, 256, 0, st, a);
+  }
+  else {       // gemm_mfma_bf16_kernel: whole tiles; ragged shapes with B (and A: bounded form) on dwords through LDS; masked
+    static const kfn kernel[2][2][4] = {      // [2 x 2 tiles][f16][exact, bounded + B through LDS, B through LDS, masked]
+      {{gemm_mfma_bf16_kernel<1, 1, true>, gemm_mfma_bf16_kernel<1, 1, false, false, true, true>, gemm_mfma_bf16_kernel<1, 1, false, false, true>, gemm_mfma_bf16_kernel<1, 1, false>},
+       {gemm_mfma_bf16_kernel<1, 1, true, true>, gemm_mfma_bf16_kernel<1, 1, false, true, true, true>, gemm_mfma_bf16_kernel<1, 1, false, true, true>, gemm_mfma_bf16_kernel<1, 1, false, true>}},
+      {{gemm_mfma_bf16_kernel<2, 2, true>, gemm_mfma_bf16_kernel<2, 2, false, false, true, true>, gemm_mfma_bf16_kernel<2, 2, false, false, true>, gemm_mfma_bf16_kernel<2, 2, false>},
+       {gemm_mfma_bf16_kernel<2, 2, true, true>, gemm_mfma_bf16_kernel<2, 2, false, true, true, true>, gemm_mfma_bf16_kernel<2, 2, false, true, true>, gemm_mfma_bf16_kernel<2, 2, false, true>}}};
+    if (f16) *name = big ? "gemm_mfma_f16_kernel<2,2>" : "gemm_mfma_f16_kernel<1,1>";
+    launch_tile(kernel[big][f16][pl.exact ? 0 : (ragged16_b_dwords(a) ? (ragged16_bounded(a) ? 1 : 2) : 3)], grid, 256, 0, st, a);
   }
   return (int)hipGetLastError();
+}
+
+// MX x MX: both operands in a block-scaled 4- / 6- / 8-bit format
+static int launch_mxmx(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  // operands are read as dwords, scales as bytes: any alignment of the leading dimensions works; bases dword aligned; offsets < 4 GiB
+  const bool ok = !a.list_a && ((a_bits(a) | b_bits(a)) & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.k < (1ll << 31);
+  if (!ok) return launch_generic(a, st, name);
+  static const kfn kernel[2][4] = {{gemm_mx_stream_kernel<1, 1, 0>, gemm_mx_stream_kernel<1, 1, 1>, gemm_mx_stream_kernel<1, 1, 2>, gemm_mx_stream_kernel<1, 1, 4>},      // [2 x 2 tiles][E4M3, E5M2, E2M3, FP4]
+                                   {gemm_mx_stream_kernel<2, 2, 0>, gemm_mx_stream_kernel<2, 2, 1>, gemm_mx_stream_kernel<2, 2, 2>, gemm_mx_stream_kernel<2, 2, 4>}};
+  if (a.a_type == LIBXSMM_DATATYPE_MXHF6) {           // E2M3 on the matrix cores (the plan sends E3M2 to the exact kernel, see plan_gemm)
+    constexpr bool small6 = false;
+    const bool big6 = pl.path == P_MXMX_2x2 && !small6;
+    const long long lim = (1ll << 31) / 3;
+    if (!((long long)a.lda * (a.k / 4) < lim && (long long)a.ldb * (a.k / 4) < lim)) return launch_generic(a, st, name);
+    constexpr int gather6 = 0;
+    a.tune = gather6;
+    const dim3 grid = wave_grid(a, big6);
+    *name = big6 ? "gemm_mx6_stream_kernel<2,2>" : "gemm_mx6_stream_kernel<1,1>";
+    launch_tile(kernel[big6][2], grid, 256, 0, st, a);
+    return (int)hipGetLastError();
+  }
+  const bool big = pl.path == P_MXMX_2x2;
+  const dim3 grid = wave_grid(a, big);
+  launch_tile(kernel[big][a.a_type == LIBXSMM_DATATYPE_MXFP4X2 ? 3 : (a.a_type == LIBXSMM_DATATYPE_MXBF8 ? 1 : 0)], grid, 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// MXFP4 weights x bf16 / f32 activations
+static int launch_mxfp4(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  // B columns 16-byte aligned (LDS-DMA); A and the scales are read byte-wise (any alignment); offsets inside a tile < 4 GiB
+  const bool ok = strided_forms(a) && ((b_bits(a) | (unsigned long long)((long long)a.ldb * 2)) & 15ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n * 2 < (1ll << 31);
+  if (!ok) return launch_generic(a, st, name);
+  static const kfn kernel[2] = {gemm_mxfp4_stream_kernel<1, 1>, gemm_mxfp4_stream_kernel<2, 2>};      // [2 x 2 tiles]
+  const bool big = pl.path == P_MX4_2x2;
+  launch_tile(kernel[big], wave_grid(a, big), 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// 8-bit floats
+static int launch_fp8(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  const bool big = pl.path == P_FP8_2x2;
+  const bool ok = strided_forms(a) && ((b_bits(a) | (unsigned long long)a.ldb) & 15ull) == 0 && (a_bits(a) & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n < (1ll << 31);
+  if (ok) {
+    const bool hf8 = a.a_type == LIBXSMM_DATATYPE_HF8, c8 = a.c_type != LIBXSMM_DATATYPE_F32;            // c8: C in the operands' type
+    // whole 32-tiles, several per problem (96^3: nine): one problem per workgroup out of LDS instead of nine waves that each fetch their own panels (gemm_wgp8_kernels.hip)
+    // (also whole 64-tiles -- 64^3 was one wave per problem: bf8 0.64 -> 0.76, i8 0.65 -> 0.75, profiles/r05_wgp_pair.jsonl; more than twelve tiles are not taken there)
+    if (a.m > 32 && a.n > 32 && (a.m / 32) * (a.n / 32) <= 12) { int taken = 0; (void)launch_gemm_wgp8(a, hf8 ? 2 : 1, false, false, st, name, &taken); if (taken) return (int)hipGetLastError(); }      // (128^3: 0.66 here against 0.43 there)
+    const dim3 grid = wave_grid(a, big);
+    if (!(c8 && a.vnni_c)) {
+      static const kfn kernel[2][2][2] = {{{gemm_fp8_stream_kernel<1, 1, false>, gemm_fp8_stream_kernel<1, 1, false, true>}, {gemm_fp8_stream_kernel<1, 1, true>, gemm_fp8_stream_kernel<1, 1, true, true>}},      // [2 x 2 tiles][hf8][c8]
+                                          {{gemm_fp8_stream_kernel<2, 2, false>, gemm_fp8_stream_kernel<2, 2, false, true>}, {gemm_fp8_stream_kernel<2, 2, true>, gemm_fp8_stream_kernel<2, 2, true, true>}}};
+      if (c8) *name = big ? "gemm_fp8c8_stream_kernel<2,2>" : "gemm_fp8c8_stream_kernel<1,1>";
+      launch_tile(kernel[big][hf8][c8], grid, 256, 0, st, a);
+      return (int)hipGetLastError();
+    }
+  }
+  return launch_m8_or_generic(a, big, st, name);            // unaligned operands, pointer / offset lists, VNNI C in the operands' type
+}
+
+// interleaved 4-bit weights with block scales x int8 activations
+static int launch_mx4i8(GemmArgs& a, const GemmPlan&, hipStream_t st, const char** name) {
+  const unsigned long long abits = a_bits(a) | (unsigned long long)(size_t)a.b_scf | (unsigned long long)a.bs_bscf;
+  const bool ok = strided_forms(a) && ((b_bits(a) | (unsigned long long)a.ldb) & 15ull) == 0 && (abits & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n < (1ll << 31) &&
+    (a.c_type == LIBXSMM_DATATYPE_F32 || a.c_type == LIBXSMM_DATATYPE_BF16) && a.a_scf && a.b_scf;
+  if (!ok) return launch_generic(a, st, name);
+  // waves that walk several consecutive tiles with the next chunk's operands in flight: at least 8 K waves per launch, at most 8 tiles each
+  constexpr int pipe = 8;
+  a.tiles_m = a.m / 32; a.tiles_n = a.n / 32; a.map2d_shift = 0;
+  const unsigned long long tiles = (unsigned long long)a.tiles_m * a.tiles_n * a.nbatch;
+  const bool c_ok = (a.flags & LIBXSMM_GEMM_FLAG_BETA_0) == 0 || (((c_bits(a) | (unsigned long long)a.bs_c2) & 15ull) == 0 &&
+    ((unsigned long long)a.ldc * (a.c_type == LIBXSMM_DATATYPE_F32 ? 4ull : 2ull)) % 16ull == 0 && !a.list_c);
+  if (pipe > 0 && c_ok && tiles < (1ull << 31) && (a.k >> 6) * a.br_count < (1ull << 31)) {
+    const unsigned int per_wave = (unsigned int)std::min<unsigned long long>((unsigned long long)pipe, std::max<unsigned long long>(1ull, tiles / 8192ull));
+    const unsigned long long waves = (tiles + per_wave - 1) / per_wave;
+    // two chunks in flight per wave at three waves per SIMD; four / six at two waves per SIMD measured the same or worse (the kernel is bound by its
+    // ~300 vector instructions per tile -- code expansion, convert / scale / add of 2 x 16 block sums -- not by the operand round trip any more)
+    hipLaunchKernelGGL((gemm_mx4i8_pipe_kernel<2>), dim3((unsigned int)((waves + 3) / 4)), dim3(256), 0, st, a, per_wave, (unsigned int)tiles);
+    *name = "gemm_mx4i8_pipe_kernel";
+    return (int)hipGetLastError();
+  }
+  launch_tile(gemm_mx4i8_stream_kernel<1, 1>, wave_grid(a, 32, 32), 256, 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// 8-bit integers, and the nibble / 2-bit / 1-bit weights that are expanded to them
+static int launch_i8(GemmArgs& a, const GemmPlan& pl, hipStream_t st, const char** name) {
+  // same alignment contract as the bf16 streaming kernel (element size 1): B columns 16-byte aligned, A dword aligned
+  const bool ok = strided_forms(a) && ((b_bits(a) | (unsigned long long)a.ldb) & 15ull) == 0 && ((a_bits(a) | c_bits(a)) & 3ull) == 0 && (long long)a.lda * a.k < (1ll << 31) && (long long)a.ldb * a.n < (1ll << 31);
+  const bool i4 = a.a_type == LIBXSMM_DATATYPE_I4X2 || a.a_type == LIBXSMM_DATATYPE_U4X2;
+  const int lowbit = a.a_type == LIBXSMM_DATATYPE_I2X4 ? 2 : (a.a_type == LIBXSMM_DATATYPE_I1X8 ? 3 : 0);
+  const bool ua = a.a_type == LIBXSMM_DATATYPE_U8, ub = a.b_type == LIBXSMM_DATATYPE_U8, big = pl.path == P_I8_2x2;
+  if (ok && i4) {
+    static const kfn kernel[2] = {gemm_i8_stream_kernel<1, 1, false, true, 1>, gemm_i8_stream_kernel<2, 2, false, true, 1>};      // [2 x 2 tiles]
+    const dim3 grid = wave_grid(a, big);
+    *name = big ? "gemm_i4_stream_kernel<2,2>" : "gemm_i4_stream_kernel<1,1>";
+    launch_tile(kernel[big], grid, 256, 0, st, a);
+    return (int)hipGetLastError();
+  }
+  if (ok && lowbit) {
+    static const kfn kernel[2][2][2] = {{{gemm_i8_stream_kernel<1, 1, false, false, 2>, gemm_i8_stream_kernel<1, 1, false, true, 2>}, {gemm_i8_stream_kernel<1, 1, false, false, 3>, gemm_i8_stream_kernel<1, 1, false, true, 3>}},      // [2 x 2 tiles][lowbit - 2][ub]
+                                        {{gemm_i8_stream_kernel<2, 2, false, false, 2>, gemm_i8_stream_kernel<2, 2, false, true, 2>}, {gemm_i8_stream_kernel<2, 2, false, false, 3>, gemm_i8_stream_kernel<2, 2, false, true, 3>}}};
+    const dim3 grid = wave_grid(a, big);
+    *name = lowbit == 2 ? (big ? "gemm_i2_stream_kernel<2,2>" : "gemm_i2_stream_kernel<1,1>") : (big ? "gemm_i1_stream_kernel<2,2>" : "gemm_i1_stream_kernel<1,1>");
+    launch_tile(kernel[big][lowbit - 2][ub], grid, 256, 0, st, a);
+    return (int)hipGetLastError();
+  }
+  if (i4 || lowbit) return launch_generic(a, st, name);
+  if (ok) {
+    if (a.m > 32 && a.n > 32 && (a.m / 32) * (a.n / 32) <= 12) { int taken = 0; (void)launch_gemm_wgp8(a, 0, ua, ub, st, name, &taken); if (taken) return (int)hipGetLastError(); }      // (as for the 8-bit floats above)
+    static const kfn kernel[2][2][2] = {{{gemm_i8_stream_kernel<1, 1, false, false>, gemm_i8_stream_kernel<1, 1, false, true>}, {gemm_i8_stream_kernel<1, 1, true, false>, gemm_i8_stream_kernel<1, 1, true, true>}},      // [2 x 2 tiles][ua][ub]
+                                        {{gemm_i8_stream_kernel<2, 2, false, false>, gemm_i8_stream_kernel<2, 2, false, true>}, {gemm_i8_stream_kernel<2, 2, true, false>, gemm_i8_stream_kernel<2, 2, true, true>}}};
+    launch_tile(kernel[big][ua][ub], wave_grid(a, big), 256, 0, st, a);
+    return (int)hipGetLastError();
+  }
+  return launch_m8_or_generic(a, big, st, name);       // unaligned operands, pointer / offset lists: the masked matrix-core kernel
+}
+
+int launch_gemm(const GemmArgs& a_in, void* stream, const char** kernel_name) {
+  hipStream_t st = (hipStream_t)stream;
+  const char* unnamed = nullptr;
+  const char** name = kernel_name ? kernel_name : &unnamed;
+  if (a_in.nbatch == 0 || a_in.m <= 0 || a_in.n <= 0) { *name = "(empty)"; return 0; }
+  if (a_in.a_type == LIBXSMM_DATATYPE_F64 && a_in.b_type == LIBXSMM_DATATYPE_F64 && a_in.c_type == LIBXSMM_DATATYPE_F64) return launch_gemm_f64(a_in, stream, kernel_name);   // gemm_f64_kernels.hip
+  GemmPlan pl = plan_gemm(a_in.m, a_in.n, a_in.k, a_in.flags, a_in.a_type, a_in.b_type, a_in.c_type, a_in.vnni_c);
+  if (a_in.comp_f16) pl = GemmPlan{P_GENERIC, false};              // a rounding after every product: only the generic kernel does that
+  if ((long long)((a_in.m + 15) / 16) * ((a_in.n + 15) / 16) * (long long)a_in.nbatch >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  *name = path_name(pl.path);
+  GemmArgs a = a_in;
+  // the families that take their shapes whatever path the plan names, in their order of precedence
+  using family = int (*)(GemmArgs&, const GemmPlan&, hipStream_t, const char**, int*);
+  static const family first[] = {launch_bf32_stream, launch_f32_blocked16, launch_bf16_macro, launch_p16, launch_f32_blocked, launch_f32_ragged, launch_bf16_forms};
+  for (const family f : first) { int taken = 0; const int e = f(a, pl, st, name, &taken); if (taken) return e; }
+  switch (pl.path) {
+    case P_F32_T16: launch_tile(gemm_mfma_f32_t16_kernel, wave_grid(a, 16, 16), 256, 0, st, a); return (int)hipGetLastError();
+    case P_F32_1x1: return launch_f32_1x1(a, pl, st, name);
+    case P_F32_2x2: return launch_f32_2x2(a, pl, st, name);
+    case P_BF16_1x1: case P_BF16_2x2: return launch_16bit(a, pl, st, name);
+    case P_W8_1x1: case P_W8_2x2: return launch_w8(a, pl, st, name);
+    case P_M8_1x1: case P_M8_2x2: return launch_m8_or_generic(a, pl.path == P_M8_2x2, st, name);
+    case P_MXMX_1x1: case P_MXMX_2x2: return launch_mxmx(a, pl, st, name);
+    case P_MX4_1x1: case P_MX4_2x2: return launch_mxfp4(a, pl, st, name);
+    case P_FP8_1x1: case P_FP8_2x2: return launch_fp8(a, pl, st, name);
+    case P_MX4I8_1x1: case P_MX4I8_2x2: return launch_mx4i8(a, pl, st, name);
+    case P_I8_1x1: case P_I8_2x2: return launch_i8(a, pl, st, name);
+    default: return launch_generic(a, st, name);
+  }
 }
 
 }  // namespace xamd
