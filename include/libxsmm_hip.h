@@ -397,6 +397,51 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemm
   size_t nsegments, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs,
   const long long* d_offs, const long long* mask_offs);
 
+/* Sliced segments: the two plain entries above with chains the CALLER has cut, so that several waves walk one long chain -- and still the same bits on every
+ * run, stream and grid size.  The entries above never split a segment, because that would reorder its sum; here the caller says where a chain may be cut, and
+ * the result is a pure function of the arguments (no atomics, no arrival order), as LIBXSMM_HIP_MEQN_ORDER_ANY of libxsmm_hip_meqn_batch_strided_accumulate is.
+ *   libxsmm_hip_gemm_batch_reduce_segments_sliced(kernel, param, nblocks, blk_ptr, nslices, seg_ptr, a_list, b_list, c_list, workspace, workspace_bytes)
+ *   libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced(kernel, param, nblocks, blk_ptr, nslices, seg_ptr, a_offs, b_offs, c_offs, workspace, workspace_bytes)
+ * A two-level CSR; a SLICE is what a segment is in the unsliced entries.  Slice j owns the products seg_ptr[j] .. seg_ptr[j+1] of a_list / b_list (a_offs /
+ * b_offs); C block b owns the slices blk_ptr[b] .. blk_ptr[b+1].  blk_ptr has nblocks + 1 non-decreasing entries, blk_ptr[0] = 0, blk_ptr[nblocks] = nslices;
+ * seg_ptr has nslices + 1 entries; c_list / c_offs has nblocks.  Every list is device-accessible and read in place: nothing is staged or uploaded, both calls
+ * can be captured into a graph.  The ADDRESS form ignores param's primary slots; the OFFSET form takes the three bases from param->{a,b,c}.primary BY VALUE,
+ * as its unsliced sibling does [ref: src/generator_gemm_reference_impl.c:509-513, :186-188].
+ * Per block b:  P_j = one accumulator chain over (product, k), in list order, over slice j, STARTED AT +0, in the accumulator type (f32 for f32 and bf16
+ * handles, f64 for f64) -- for f32 the k-ordered fmaf chain bit for bit, in every transpose form; an empty slice gives +0.  acc = C(i,j) widened to the
+ * accumulator type (beta = 1) or +0 (beta = 0); for j ascending over the block's slices acc = acc + P_j, each one IEEE add in the accumulator type with
+ * denormals kept; acc is stored with one rounding through the library's bf16 conversion for a bf16 C.  Bytes of the C block outside m x n stay the caller's.
+ * A block with no slices: beta = 0 stores +0, beta = 1 leaves the block untouched.  Consequences: with beta = 0 and one slice per block the result is bitwise
+ * the unsliced call's (a chain started at +0 never yields -0, so +0 + P is P); with beta = 1 the original C is ADDED TO the first partial, not used as the
+ * chain's start -- the documented difference from the unsliced entries, as in ORDER_ANY.  Blocks whose C overlaps are undefined; A and B blocks may be shared.
+ * Meant for FEW blocks with LONG chains (the weight gradient of a block-sparse layer, dW_b = sum_n dY_n X_n^T with TRANS_B: hundreds of blocks, hundreds of
+ * products each) and for the long tail of a skewed list; NOT for many short chains, where the second launch and the partials' round trip through memory are
+ * pure overhead (DESIGN.md section 9.5 has the measurements).  The library chooses no slice lengths.
+ * The workspace is the caller's: it holds the slice partials, its layout is the library's business and its contents after the call are unspecified.
+ *   libxsmm_hip_gemm_batch_reduce_segments_sliced_workspace(kernel, nslices)
+ * is the only authority on its size: a multiple of 16, 0 for nslices = 0, at least nslices * m * n * sizeof(acc) and at most nslices * the tile-padded block;
+ * 0 with the handle's refusal code set for an ineligible handle (it serves both forms).  `workspace` must be 16-byte aligned and device-accessible,
+ * workspace_bytes at least the query's value; nothing beyond that value is written.
+ * Eligible handles: exactly those of libxsmm_hip_gemm_batch_reduce_segments (ADDRESS form) and of libxsmm_hip_gemm_batch_reduce_segments_offsets (OFFSET form,
+ * with TRANS_A / TRANS_B under its rules).  Ext handles are refused: a fused epilogue over slices is out of scope.  Errors are set before anything is
+ * launched, one per refusal.  -2: param, blk_ptr, c_list / c_offs or an OFFSET base is NULL while nblocks > 0; seg_ptr, a_*, b_* or workspace is NULL while
+ * nslices > 0; workspace_bytes below the query's value.  -3: every handle refusal of the sibling entry, in its words; a workspace that is not 16-byte
+ * aligned.  -4: no device.  nblocks = 0 does nothing.  Follows the thread's launch mode like the siblings (blocking, stream-ordered, coalescing: flushed
+ * first, pipeline section).  A call is TWO kernel launches in order on the same stream or the same pipeline lane -- the slices' partials, then the blocks'
+ * sums (gemm_segments_slice_reduce_kernel<cls>); with nslices = 0 the first is skipped.  libxsmm_hip_launch_count counts both;
+ * libxsmm_hip_kernel_name(kernel, 1) names the first (gemm_segments_sliced_f32_kernel, _bf16_kernel, _f64_kernel;
+ * gemm_segments_offs_sliced_f32_kernel<ta,tb>, _bf16_kernel<ta,tb>, _f64_kernel<ta,tb>).
+ */
+LIBXSMM_API size_t libxsmm_hip_gemm_batch_reduce_segments_sliced_workspace(libxsmm_gemmfunction kernel, size_t nslices);
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_sliced(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
+  size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list,
+  void* workspace, size_t workspace_bytes);
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
+  size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs,
+  void* workspace, size_t workspace_bytes);
+
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns
  * [begin, end) of a `count`-long axis (first `count % world` ranks get one extra unit),

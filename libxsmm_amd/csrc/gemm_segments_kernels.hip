@@ -27,7 +27,10 @@
 // the tiles.  The two transposes are template parameters of the kernels, four instances per class: as wave-uniform runtime bits that select the tile instance
 // inside ONE kernel they cost 196 / 224 / 88 registers (f32 / bf16 / f64: a wave per SIMD less for f32, two less for f64), although no single form needs more
 // than the ADDRESS kernels' 160 / 196 / 72 -- the register allocator does not keep the four bodies apart (DESIGN.md section 9.2 has the numbers).
+// The two *_sliced entries (further down) let the CALLER cut a chain: pass 1 is the same item loop over (slice, tile) with the partials
+// of a workspace as destinations, pass 2 adds a block's partials in ascending slice order.  The entries above never split a segment.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "internal.hpp"
 #include "gemm_device.hpp"
 #include "bf16_cvt.hpp"
@@ -146,8 +149,127 @@ XAMD_OFFS_FUSED_KERNEL(gemm_segments_offs_f32_fused_kernel, 0)
 XAMD_OFFS_FUSED_KERNEL(gemm_segments_offs_bf16_fused_kernel, 1)
 #undef XAMD_OFFS_FUSED_KERNEL
 
+// ---- sliced segments (libxsmm_hip_gemm_batch_reduce_segments_sliced, ..._offsets_sliced): a chain cut into slices that separate waves walk ------------------
+// Pass 1 is the item loop above with one more policy: the item is (slice, tile), and a slice's destination is not a caller's block but its partial in the
+// workspace, g.c + slice * g.sc -- computed, no list is read for it.  The GemmGroupDesc of pass 1 has beta = 0, an accumulator-typed C (f32 for the f32 and
+// bf16 classes, f64) and ldc = m: the partial is the dense m x n block, each 16-byte aligned (g.sc is m * n accumulators rounded up to 16 bytes).  The chain
+// is the base source's, so a slice is the (product, k) chain of a segment started at +0, bit for bit; an empty slice stores +0.
+template <typename Base> struct SlicedSource {
+  Base base;
+  __device__ __forceinline__ gptr c(const GemmGroupDesc& g, unsigned long long s) const { return (gptr)g.c + (long long)s * g.sc; }
+  __device__ __forceinline__ auto chain(const GemmGroupDesc& g, unsigned long long r0, unsigned long long r1) const { return base.chain(g, r0, r1); }
+};
+
+#define XAMD_SEG_SLICED_KERNEL(NAME, CLS) \
+  __global__ __launch_bounds__(256) void NAME(GemmGroupDesc g, const unsigned long long* __restrict__ seg_ptr, const void* const* __restrict__ a_list, \
+    const void* const* __restrict__ b_list, unsigned long long total) { \
+    segments_items<CLS, false, false>(g, seg_ptr, SlicedSource<ListSource>{ListSource{a_list, b_list, nullptr}}, NoSegEpilogue{}, total); }
+XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_f32_kernel, 0)
+XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_bf16_kernel, 1)
+XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_f64_kernel, 2)
+#undef XAMD_SEG_SLICED_KERNEL
+
+#define XAMD_OFFS_SLICED_KERNEL(NAME, CLS) \
+  template <bool TA, bool TB> __global__ __launch_bounds__(256) void NAME(GemmGroupDesc g, int a_wide, const unsigned long long* __restrict__ seg_ptr, \
+    const long long* __restrict__ a_offs, const long long* __restrict__ b_offs, unsigned long long total) { \
+    segments_items<CLS, TA, TB>(g, seg_ptr, SlicedSource<OffsetSource<int>>{OffsetSource<int>{a_offs, b_offs, nullptr, a_wide}}, NoSegEpilogue{}, total); }
+XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_f32_kernel, 0)
+XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_bf16_kernel, 1)
+XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_f64_kernel, 2)
+#undef XAMD_OFFS_SLICED_KERNEL
+
+// Pass 2: acc = C (beta = 1) or +0, then acc += P_j for the block's slices j in ASCENDING order -- one IEEE add each in the accumulator type (the kernels run
+// with denormals kept), no atomics, no arrival order -- then one store with C's ldc and type.  CLS: 0 f32 partials -> f32 C, 1 f32 partials -> bf16 C
+// (bf16_cvt.hpp: one rounding), 2 f64.  Bandwidth-bound: a work item is (block, run of 64 x V elements of the dense partial), V = 16 bytes of accumulators, so
+// lane l owns the elements (64 run + l) V .. + V - 1 of EVERY slice of the block and a wave's load of one slice is 1 KiB contiguous.  Four slices' loads are in
+// flight before the first add; a block's last one to three slices go one by one.  A lane's last load may reach past m * n into the partial's padding (inside
+// the workspace by construction of g.sc; never added into anything stored).  blk_ptr[b], blk_ptr[b + 1] and C's entry are wave-uniform scalar loads like the
+// item heads of pass 1, and the waves grid-stride in the same way.  C is read only under beta = 1 and written for i < m, j < n only: with m a multiple of V and
+// columns and block V-element aligned (`wide_ld`, then the pointer) a lane's V elements are one load / store of C, else element by element.  A block without
+// slices: beta = 0 stores +0, beta = 1 is skipped.  No LDS, no scratch, vector stores only.
+template <int CLS>
+__global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSliceReduce q, unsigned long long total) {
+  typedef typename std::conditional<CLS == 2, double, float>::type acc_t;
+  typedef typename std::conditional<CLS == 2, double, typename std::conditional<CLS == 1, unsigned short, float>::type>::type c_t;
+  constexpr int V = 16 / (int)sizeof(acc_t);
+  typedef acc_t vec_t __attribute__((ext_vector_type(V)));
+  typedef c_t cvec_t __attribute__((ext_vector_type(V)));
+  const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned int lane = threadIdx.x & 63u;
+  const unsigned long long step = (unsigned long long)gridDim.x * 4u;
+  const unsigned int mn = (unsigned int)q.m * (unsigned int)q.n;
+  for (unsigned long long item = (unsigned long long)blockIdx.x * 4u + wave; item < total; item += step) {
+    unsigned long long b = item; unsigned int run = 0;
+    if (q.runs != 1) { b = item / q.runs; run = (unsigned int)(item - b * q.runs); }
+    const unsigned long long s0 = uniform_u64(((GM const unsigned long long*)q.blk_ptr)[b]), s1 = uniform_u64(((GM const unsigned long long*)q.blk_ptr)[b + 1]);
+    if (s0 == s1 && q.beta1) continue;
+    gptr c = q.c_base ? (gptr)q.c_base + (long long)uniform_u64(((GM const unsigned long long*)q.c_list)[b]) : (gptr)list_entry(q.c_list, b);
+    const unsigned int e0 = (run * 64u + lane) * (unsigned int)V;
+    const bool live = e0 < mn;
+    const unsigned int el = live ? e0 : 0u;                                      // lanes past the block re-read its first elements and store nothing
+    const unsigned int j0 = el / (unsigned int)q.m, i0 = el - j0 * (unsigned int)q.m;
+    const bool wide = q.wide_ld && ((unsigned int)(size_t)c & (unsigned int)(V * sizeof(c_t) - 1)) == 0;
+    GM c_t* cw = (GM c_t*)c + ((long long)j0 * q.ldc + i0);                      // wide: the lane's V elements of one column
+    vec_t acc;
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = (acc_t)0;
+    if (q.beta1) {
+      if (wide) {
+        const cvec_t x = *(GM const cvec_t*)cw;
+#pragma unroll
+        for (int v = 0; v < V; ++v) { if constexpr (CLS == 1) acc[v] = bf16_bits_to_f32(x[v]); else acc[v] = x[v]; }
+      } else {
+        unsigned int i = i0, j = j0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          if (live && e0 + v < mn) {
+            const c_t x = ((GM const c_t*)c)[(long long)j * q.ldc + i];
+            if constexpr (CLS == 1) acc[v] = bf16_bits_to_f32(x); else acc[v] = x;
+          }
+          if (++i == (unsigned int)q.m) { i = 0; ++j; }
+        }
+      }
+    }
+    gcptr p = (gcptr)q.ws + (long long)s0 * q.pstride + (long long)el * (long long)sizeof(acc_t);
+    unsigned long long s = s0;
+    for (; s + 4 <= s1; s += 4) {
+      const vec_t x0 = *(GM const vec_t*)p, x1 = *(GM const vec_t*)(p + q.pstride), x2 = *(GM const vec_t*)(p + 2 * q.pstride), x3 = *(GM const vec_t*)(p + 3 * q.pstride);
+      p += 4 * q.pstride;
+      acc += x0; acc += x1; acc += x2; acc += x3;
+    }
+    for (; s < s1; ++s) { acc += *(GM const vec_t*)p; p += q.pstride; }
+    if (!live) continue;
+    if constexpr (CLS == 1) {
+      float x[V]; unsigned int pk[V / 2];
+#pragma unroll
+      for (int v = 0; v < V; ++v) x[v] = acc[v];
+      bf16_pk_exact_n<V / 2>(x, pk);
+      if (wide) { u32x2 w = {pk[0], pk[1]}; *(GM u32x2*)cw = w; }
+      else {
+        unsigned int i = i0, j = j0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          if (e0 + v < mn) ((GM unsigned short*)c)[(long long)j * q.ldc + i] = (unsigned short)((v & 1) ? (pk[v / 2] >> 16) : (pk[v / 2] & 0xffffu));
+          if (++i == (unsigned int)q.m) { i = 0; ++j; }
+        }
+      }
+    } else if (wide) *(GM vec_t*)cw = acc;
+    else {
+      unsigned int i = i0, j = j0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        if (e0 + v < mn) ((GM acc_t*)c)[(long long)j * q.ldc + i] = acc[v];
+        if (++i == (unsigned int)q.m) { i = 0; ++j; }
+      }
+    }
+  }
+}
+
 // the four instances of an offsets kernel, indexed by forms & 3 (bit 0 TRANS_A, bit 1 TRANS_B)
 #define XAMD_FORMS(NAME) {NAME "<0,0>", NAME "<1,0>", NAME "<0,1>", NAME "<1,1>"}
+static const char* const kSlicedNames[3] = {"gemm_segments_sliced_f32_kernel", "gemm_segments_sliced_bf16_kernel", "gemm_segments_sliced_f64_kernel"};
+static const char* const kOffsSlicedNames[3][4] = {XAMD_FORMS("gemm_segments_offs_sliced_f32_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf16_kernel"),
+  XAMD_FORMS("gemm_segments_offs_sliced_f64_kernel")};
 static const char* const kListNames[5] = {"gemm_segments_f32_kernel", "gemm_segments_bf16_kernel", "gemm_segments_f64_kernel", "gemm_segments_f32_fused_kernel",
   "gemm_segments_bf16_fused_kernel"};
 static const char* const kOffsNames[5][4] = {XAMD_FORMS("gemm_segments_offs_f32_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_kernel"), XAMD_FORMS("gemm_segments_offs_f64_kernel"),
@@ -180,7 +302,53 @@ static void launch_list(const SegmentsLaunch& l, unsigned int grid, hipStream_t 
   else hipLaunchKernelGGL(gemm_segments_f32_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
 }
 
+template <bool TA, bool TB>
+static void launch_offs_sliced_form(const SegmentsLaunch& l, const GemmGroupDesc& g, unsigned int grid, hipStream_t st) {
+  const long long* a_offs = (const long long*)l.a_list; const long long* b_offs = (const long long*)l.b_list;
+  const int a_wide = (l.forms >> 2) & 3;
+  if (l.cls == 2) hipLaunchKernelGGL((gemm_segments_offs_sliced_f64_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
+  else if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_sliced_bf16_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
+  else hipLaunchKernelGGL((gemm_segments_offs_sliced_f32_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
+}
+
+// The two launches of a sliced call, in order on one stream: the slices' partials into the workspace (skipped without slices), then the blocks' sums.
+static int launch_sliced(const SegmentsLaunch& l, hipStream_t st, const char** kname) {
+  *kname = l.offsets ? kOffsSlicedNames[l.cls][l.forms & 3] : kSlicedNames[l.cls];
+  const int V = l.cls == 2 ? 2 : 4;                        // accumulators in 16 bytes
+  if (l.items != 0) {
+    GemmGroupDesc g = l.g;                                 // pass 1 writes partials: beta = 0, accumulator-typed, dense, `pstride` bytes apart in the workspace
+    g.beta1 = 0; g.c_bf16 = 0; g.ldc = g.m; g.c = (char*)l.workspace; g.sc = l.pstride;
+    const unsigned int grid = group_grid(l.items);
+    if (!l.offsets) {
+      const void* const* a_list = (const void* const*)l.a_list; const void* const* b_list = (const void* const*)l.b_list;
+      if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_sliced_f64_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+      else if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_sliced_bf16_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+      else hipLaunchKernelGGL(gemm_segments_sliced_f32_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+    } else switch (l.forms & 3) {
+      case 0: launch_offs_sliced_form<false, false>(l, g, grid, st); break;
+      case 1: launch_offs_sliced_form<true, false>(l, g, grid, st); break;
+      case 2: launch_offs_sliced_form<false, true>(l, g, grid, st); break;
+      default: launch_offs_sliced_form<true, true>(l, g, grid, st); break;
+    }
+    const int err = (int)hipGetLastError();
+    if (err != 0) return err;
+  }
+  GemmSliceReduce q;
+  q.blk_ptr = l.blk_ptr; q.c_list = l.c_list; q.c_base = l.offsets ? l.g.c : nullptr; q.ws = (const char*)l.workspace; q.pstride = l.pstride;
+  q.m = l.g.m; q.n = l.g.n; q.ldc = l.g.ldc; q.beta1 = l.g.beta1;
+  const unsigned long long mn = (unsigned long long)l.g.m * (unsigned long long)l.g.n;
+  q.runs = slice_reduce_runs(mn, l.cls);
+  q.wide_ld = (l.g.m % V == 0 && l.g.ldc % V == 0) ? 1 : 0;      // a lane's V elements as one load / store of C: inside one column, V-element aligned
+  const unsigned long long total = l.nblocks * q.runs;
+  const unsigned int grid = group_grid(total);
+  if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<2>, dim3(grid), dim3(256), 0, st, q, total);
+  else if (l.g.c_bf16) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<1>, dim3(grid), dim3(256), 0, st, q, total);
+  else hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<0>, dim3(grid), dim3(256), 0, st, q, total);
+  return (int)hipGetLastError();
+}
+
 int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname) {
+  if (l.sliced) return launch_sliced(l, (hipStream_t)stream, kname);
   const int row = l.fused ? (l.cls == 1 ? 4 : 3) : l.cls;
   *kname = l.offsets ? kOffsNames[row][l.forms & 3] : kListNames[row];
   if (l.items == 0) return 0;

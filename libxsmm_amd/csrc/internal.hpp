@@ -314,7 +314,7 @@ int launch_brsplit_reduce(const GemmArgs& args, const float* partial, int nsplit
 // the grid of the grouped and the segment kernels (four waves a workgroup, a wave per work item): one wave per item up to 32 768 workgroups (16 rounds of the
 // chip's resident waves); beyond that the waves grid-stride
 inline unsigned int group_grid(unsigned long long items) { return (unsigned int)((items + 3) / 4 < 32768ull ? (items + 3) / 4 : 32768ull); }
-// gemm_segments_kernels.hip: one launch of the four libxsmm_hip_gemm_*batch_reduce_segments* entries.  `g` carries the shape, leading dimensions, beta, layout
+// gemm_segments_kernels.hip: one launch of the four libxsmm_hip_gemm_*batch_reduce_segments* entries (the two *_sliced entries: two).  `g` carries the shape, leading dimensions, beta, layout
 // bits, tile edge and what the leading dimensions allow of the wider loads (a_vec4 / b_vec16 / b_vec8); its stride and prefix slots are unused.  The lists are
 // device-accessible: pointers, or (offsets) signed byte offsets from the three bases in g.a / g.b / g.c.
 struct SegmentsLaunch {
@@ -325,8 +325,26 @@ struct SegmentsLaunch {
   const void* a_list; const void* b_list; const void* c_list;
   bool offsets, fused;                              // fused: the ext ABI's epilogue (column bias, ReLU (+ bitmask), sigmoid) in the store; cls 0 or 1
   const void* epilogue;                             // fused: the GemmSegEpilogue, with offsets the GemmSegOffsEpilogue
+  // the two *_sliced entries: `seg_ptr`, `a_list`, `b_list` and `items` are the SLICES' (items = slices x C tiles), `c_list` has one entry per block, and the
+  // call is two launches: the slices' partials into `workspace`, `pstride` bytes apart, then the blocks' sums over blk_ptr (GemmSliceReduce)
+  bool sliced;
+  unsigned long long nblocks; const unsigned long long* blk_ptr;
+  void* workspace; long long pstride;
 };
-int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname);   // *kname: the kernel instance of class x forms x fused x offsets
+// pass 2 of a sliced call (gemm_segments_slice_reduce_kernel), by value in the kernel arguments
+struct GemmSliceReduce {
+  const unsigned long long* blk_ptr;                // nblocks + 1: block b owns the partials blk_ptr[b] .. blk_ptr[b + 1]
+  const void* c_list;                               // nblocks pointers, or (c_base != NULL) signed byte offsets from c_base
+  char* c_base;
+  const char* ws; long long pstride;                // partial j: the dense m x n accumulator block at ws + j * pstride (16-byte aligned)
+  int m, n, ldc, beta1;
+  unsigned int runs;                                // work items of one block: runs of 64 lanes x 16 bytes of accumulators
+  int wide_ld;                                      // m and ldc are multiples of the elements in 16 bytes of accumulators: a lane's run lies in one column of C
+};
+// bytes between the partials of a sliced call: m x n accumulators (f64 for class 2, else f32), rounded up to 16
+inline unsigned long long slice_partial_stride(unsigned long long mn, int cls) { return (mn * (cls == 2 ? 8u : 4u) + 15u) & ~15ull; }
+inline unsigned int slice_reduce_runs(unsigned long long mn, int cls) { const unsigned int per = cls == 2 ? 128u : 256u; return (unsigned int)((mn + per - 1) / per); }
+int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname);   // *kname: the kernel instance of class x forms x fused x offsets (sliced: of pass 1)
 int launch_spmm(const SpmmArgs& args, void* stream, const char** kernel_name);
 int launch_bcsc(const BcscArgs& args, void* stream, const char** kernel_name);
 // Automatic streaming decision (libxsmm_hip_set_streaming_hint(0)): a launch whose own operands exceed the Infinity Cache streams -- and so does a launch whose operands

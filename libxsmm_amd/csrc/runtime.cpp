@@ -2577,19 +2577,40 @@ LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan
 // entry (the two libxsmm_hip_gemm_ext_batch_reduce_segments* entries take ext handles and only those); `forms` != NULL is one of the two *_offsets entries, which
 // take OFFSET handles, three bases in param's primary slots (the lists are then a_offs / b_offs / c_offs) and transposed operands: *forms receives the bits
 // their kernels read.  (a, b and c sit at the same place in libxsmm_gemm_param and libxsmm_gemm_ext_param.)  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64) and `tiles` the C tiles of one segment.
+struct SegmentsSliced;
+static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, GemmGroupDesc& g, int& cls, unsigned long long& tiles,
+  int* forms, const SegmentsSliced* sl);
+// The two *_sliced entries add the second level of their CSR and the caller's workspace: `nsegments`, `seg_ptr`, `a_list` and `b_list` are then the SLICES', c_list
+// has one entry per block.
+struct SegmentsSliced { size_t nblocks; const unsigned long long* blk_ptr; void* workspace; size_t workspace_bytes; };
 static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, const unsigned long long* seg_ptr,
-  const void* a_list, const void* b_list, const void* c_list, GemmGroupDesc& g, int& cls, unsigned long long& tiles, int* forms = nullptr) {
+  const void* a_list, const void* b_list, const void* c_list, GemmGroupDesc& g, int& cls, unsigned long long& tiles, int* forms = nullptr, const SegmentsSliced* sl = nullptr) {
   const bool offsets = forms != nullptr;
-  if (!param || !seg_ptr || !a_list || !b_list || !c_list) {
+  if (sl) {                                                 // nblocks > 0 here; the slices' arrays and the workspace are only needed when there are slices
+    if (!param || !sl->blk_ptr || !c_list) {
+      set_error(-2, "%s: %s is NULL but nblocks = %zu", fn, !param ? "param" : (!sl->blk_ptr ? "blk_ptr" : (offsets ? "c_offs" : "c_list")), sl->nblocks); return nullptr;
+    }
+    if (nsegments > 0 && (!seg_ptr || !a_list || !b_list || !sl->workspace)) {
+      set_error(-2, "%s: %s is NULL but nslices = %zu", fn, !seg_ptr ? "seg_ptr" : (!a_list ? (offsets ? "a_offs" : "a_list") : (!b_list ? (offsets ? "b_offs" : "b_list") : "workspace")), nsegments);
+      return nullptr;
+    }
+  } else if (!param || !seg_ptr || !a_list || !b_list || !c_list) {
     set_error(-2, "%s: %s is NULL but nsegments = %zu", fn, !param ? "param" : (!seg_ptr ? "seg_ptr" : (!a_list ? (offsets ? "a_offs" : "a_list") : (!b_list ? (offsets ? "b_offs" : "b_list") :
       (offsets ? "c_offs" : "c_list")))), nsegments); return nullptr;
   }
   if (offsets) {
     const libxsmm_gemm_param* q = (const libxsmm_gemm_param*)param;
     if (!q->a.primary || !q->b.primary || !q->c.primary) {
-      set_error(-2, "%s: param->%s.primary (the base the offsets are added to) is NULL but nsegments = %zu", fn, !q->a.primary ? "a" : (!q->b.primary ? "b" : "c"), nsegments); return nullptr;
+      set_error(-2, "%s: param->%s.primary (the base the offsets are added to) is NULL but %s = %zu", fn, !q->a.primary ? "a" : (!q->b.primary ? "b" : "c"), sl ? "nblocks" : "nsegments",
+        sl ? sl->nblocks : nsegments); return nullptr;
     }
   }
+  return segments_handle(fn, ext, kernel, param, nsegments, g, cls, tiles, forms, sl);
+}
+// The handle's half of segments_validate (`param` != NULL: the OFFSET bases are taken from it), which is all the workspace query of the sliced entries asks.
+static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, GemmGroupDesc& g, int& cls, unsigned long long& tiles,
+  int* forms, const SegmentsSliced* sl) {
+  const bool offsets = forms != nullptr;
   KernelCtx* k = ctx_from_handle(kernel);
   if (!k) { set_error(-3, "%s: unknown kernel handle", fn); return nullptr; }
   if (k->kind != K_GEMM) { set_error(-3, "%s: handle is not a BRGEMM kernel (TPP, equation and sparse handles are not taken)", fn); return nullptr; }
@@ -2626,12 +2647,17 @@ static KernelCtx* segments_validate(const char* fn, bool ext, const void* kernel
   g.a_vec4 = cls == 1 ? 1 : 0; g.b_vec16 = (!tb && (colb & 15) == 0) ? 1 : 0; g.b_vec8 = (!tb && (colb & 7) == 0) ? 1 : 0;
   if (offsets) {
     const libxsmm_gemm_param* q = (const libxsmm_gemm_param*)param;
-    g.a = (const char*)q->a.primary; g.b = (const char*)q->b.primary; g.c = (char*)q->c.primary;
+    if (q) { g.a = (const char*)q->a.primary; g.b = (const char*)q->b.primary; g.c = (char*)q->c.primary; }
     const unsigned long long rowb = (unsigned long long)d.lda * esz;          // a transposed A: the k run of a row takes B's wide loads
     *forms = (ta ? 1 : 0) | (tb ? 2 : 0) | ((ta && (rowb & 15) == 0) ? 4 : 0) | ((ta && (rowb & 7) == 0) ? 8 : 0);
   }
   tiles = (unsigned long long)g.tiles_m * (unsigned long long)g.tiles_n;
-  if (tiles != 0 && (unsigned long long)nsegments > ~0ull / tiles - 4) { set_error(-3, "%s: nsegments x C tiles overflows 64 bits", fn); return nullptr; }
+  if (tiles != 0 && (unsigned long long)nsegments > ~0ull / tiles - 4) { set_error(-3, "%s: %s x C tiles overflows 64 bits", fn, sl ? "nslices" : "nsegments"); return nullptr; }
+  if (sl && tiles != 0) {                                   // the work items of pass 2 and the workspace's bytes
+    const unsigned long long mn = (unsigned long long)d.m * d.n;
+    if ((unsigned long long)sl->nblocks > ~0ull / slice_reduce_runs(mn, cls) - 4) { set_error(-3, "%s: nblocks x element runs overflows 64 bits", fn); return nullptr; }
+    if ((unsigned long long)nsegments > (unsigned long long)(~(size_t)0 >> 1) / slice_partial_stride(mn, cls)) { set_error(-3, "%s: nslices x the partial's bytes overflows", fn); return nullptr; }
+  }
   return k;
 }
 // The operators of an ext handle as the fused segment kernels take them, decoded as run_gemm decodes them: colbias, and act 0 none, 1 ReLU, 2 ReLU + bitmask,
@@ -2650,13 +2676,22 @@ static bool segments_operators(const char* fn, const libxsmm_gemm_descriptor& d,
 // [ref: gemm ref :294-372]; the bias and mask blocks come from d_list / mask_list, or from param->d.primary / param->c.secondary plus their offsets (without
 // d_list the one bias is shared).  Nothing is staged, so every one of the four calls can be captured.
 static void run_segments(const char* fn, bool ext, bool offsets, const void* kernel, const void* param, size_t nsegments, const unsigned long long* seg_ptr,
-  const void* a_list, const void* b_list, const void* c_list, const void* d_list, const void* mask_list) {
-  if (nsegments == 0) return;
+  const void* a_list, const void* b_list, const void* c_list, const void* d_list, const void* mask_list, const SegmentsSliced* sl = nullptr) {
+  if (sl ? sl->nblocks == 0 : nsegments == 0) return;
   SegmentsLaunch l;
   std::memset(&l, 0, sizeof(l));
   unsigned long long tiles = 0;
-  KernelCtx* k = segments_validate(fn, ext, kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, l.g, l.cls, tiles, offsets ? &l.forms : nullptr);
+  KernelCtx* k = segments_validate(fn, ext, kernel, param, nsegments, seg_ptr, a_list, b_list, c_list, l.g, l.cls, tiles, offsets ? &l.forms : nullptr, sl);
   if (!k) return;
+  if (sl) {
+    l.sliced = true; l.nblocks = sl->nblocks; l.blk_ptr = sl->blk_ptr; l.workspace = sl->workspace;
+    l.pstride = (long long)slice_partial_stride((unsigned long long)k->g.m * k->g.n, l.cls);
+    const size_t need = nsegments * (size_t)l.pstride;
+    if (sl->workspace_bytes < need) {
+      set_error(-2, "%s: workspace_bytes = %zu is below the %zu bytes that libxsmm_hip_gemm_batch_reduce_segments_sliced_workspace(kernel, %zu) asks for", fn, sl->workspace_bytes, need, nsegments); return;
+    }
+    if (((size_t)sl->workspace & 15u) != 0) { set_error(-3, "%s: workspace is not 16-byte aligned", fn); return; }
+  }
   GemmSegEpilogue e; GemmSegOffsEpilogue eo;
   if (ext) {
     const libxsmm_gemm_ext_param* p = (const libxsmm_gemm_ext_param*)param;
@@ -2699,6 +2734,7 @@ static void run_segments(const char* fn, bool ext, bool offsets, const void* ker
   const char* kname = nullptr;
   const int err = launch_gemm_segments(l, tls().stream, &kname);
   k->kname_batched = kname;
+  if (sl && l.items != 0 && err == 0) ++tls().launches;  // a sliced call is two launches on ONE stream (or lane): the lane advances once, below
   finish_launch(err, kname);
 }
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nsegments,
@@ -2716,6 +2752,28 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunc
 LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param, size_t nsegments,
   const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs, const long long* d_offs, const long long* mask_offs) {
   run_segments("libxsmm_hip_gemm_ext_batch_reduce_segments_offsets", true, true, (const void*)kernel, param, nsegments, seg_ptr, a_offs, b_offs, c_offs, d_offs, mask_offs);
+}
+// The sliced forms of the two plain entries (include/libxsmm_hip.h): the caller cuts the chains, the library sums each slice as a segment of its own into the
+// caller's workspace and adds a block's partials in ascending slice order -- two launches, the same bits on every run.
+LIBXSMM_API size_t libxsmm_hip_gemm_batch_reduce_segments_sliced_workspace(libxsmm_gemmfunction kernel, size_t nslices) {
+  const char* fn = "libxsmm_hip_gemm_batch_reduce_segments_sliced_workspace";
+  const KernelCtx* peek = ctx_from_handle((const void*)kernel);
+  const bool offsets = peek && peek->kind == K_GEMM && (peek->g.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET) != 0;   // either form's handles; every other handle gets the ADDRESS entry's words
+  GemmGroupDesc g; int cls = 0, forms = 0; unsigned long long tiles = 0;
+  const SegmentsSliced sl = {1, nullptr, nullptr, 0};
+  const KernelCtx* k = segments_handle(fn, false, (const void*)kernel, nullptr, nslices, g, cls, tiles, offsets ? &forms : nullptr, &sl);
+  if (!k || tiles == 0) return 0;
+  return nslices * (size_t)slice_partial_stride((unsigned long long)k->g.m * k->g.n, cls);
+}
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_sliced(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list, void* workspace, size_t workspace_bytes) {
+  const SegmentsSliced sl = {nblocks, blk_ptr, workspace, workspace_bytes};
+  run_segments("libxsmm_hip_gemm_batch_reduce_segments_sliced", false, false, (const void*)kernel, param, nslices, seg_ptr, a_list, b_list, c_list, nullptr, nullptr, &sl);
+}
+LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param, size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs, void* workspace, size_t workspace_bytes) {
+  const SegmentsSliced sl = {nblocks, blk_ptr, workspace, workspace_bytes};
+  run_segments("libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced", false, true, (const void*)kernel, param, nslices, seg_ptr, a_offs, b_offs, c_offs, nullptr, nullptr, &sl);
 }
 // ---- multi-device launch from ONE host thread (the reference's scale-out axis is the caller's loop,
 // samples/xgemm/gemm_kernel.c:4063-4066) --------------------------------------------------------------------------------------------------------
