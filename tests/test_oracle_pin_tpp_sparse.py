@@ -153,6 +153,69 @@ def test_gather_bit_identical(reference, dt, mode, idx8):
     assert np.array_equal(a, b)
 
 
+# ---- the rest of the data-movement family (tests/meltw_move_helpers.py): the whole poisoned output allocation, oracle against reference -------------------------
+# The twelve transform types the table above does not hold, at the minimal shapes of tests/test_meltw_move_gpu.py and a payload type the reference's
+# libxsmm_elementwise_transform_kernel has a branch for [ref: mateltwise ref :966-1062].
+MORE_TRANSFORMS = [
+    (UNARY.TRANSFORM_NORM_TO_VNNI8, DT.BF16), (UNARY.TRANSFORM_NORM_TO_VNNI8, DT.I8), (UNARY.TRANSFORM_NORM_TO_VNNI2_PAD, DT.BF16), (UNARY.TRANSFORM_NORM_TO_VNNI4_PAD, DT.I8),
+    (UNARY.TRANSFORM_NORM_TO_VNNI4_PAD, DT.F16), (UNARY.TRANSFORM_NORM_TO_VNNI8_PAD, DT.BF16), (UNARY.TRANSFORM_VNNI8_TO_VNNI8T, DT.BF16), (UNARY.TRANSFORM_VNNI8_TO_VNNI8T, DT.I8),
+    (UNARY.TRANSFORM_NORM_TO_VNNI8T, DT.BF16), (UNARY.TRANSFORM_VNNI2T_TO_NORM, DT.BF16), (UNARY.TRANSFORM_VNNI4T_TO_NORM, DT.BF16), (UNARY.TRANSFORM_VNNI8T_TO_NORM, DT.BF16),
+    (UNARY.TRANSFORM_PADM_MOD4, DT.I8), (UNARY.TRANSFORM_PADN_MOD4, DT.I8), (UNARY.TRANSFORM_PADNM_MOD2, DT.BF16),
+]
+# what the reference cannot run, and why it is not in a table
+NOT_PINNED = {
+    "GATHER / SCATTER of 8-byte payloads": "libxsmm_elementwise_gather_scatter_kernel has branches for 32-, 16- and 8-bit payloads only [ref: mateltwise ref :1451-1453, "
+                                           ":1489-1790]: with F64 / I64 it returns without moving anything (held by test_reference_moves_no_8_byte_payload below); the "
+                                           "8-byte instantiations are held against move_numpy's restatement of the same loops in tests/test_meltw_move_cpu.py",
+    "transforms at 4- and 8-byte payloads (the transpose apart)": "libxsmm_elementwise_transform_kernel dispatches on 16- and 8-bit types only [ref: :966-1062]",
+    "NORM_TO_VNNIv with n % v != 0": "the reference copies the rows n .. Nn - 1 from behind the input matrix [ref: :547-553]; the oracle keeps the zero fill of the same "
+                                     "function: the pinned shapes have n % v == 0",
+}
+
+
+def _pin_whole_allocation(reference, case):
+    a, b = case.run_oracle(), case.run_reference(reference)
+    assert np.array_equal(a, b), f"{case.id()}: {np.count_nonzero(a != b)} bytes differ; first at {int(np.flatnonzero(a != b)[0])}"
+    assert not np.array_equal(a, case.out0)
+
+
+@pytest.mark.parametrize("typ,dt", MORE_TRANSFORMS, ids=lambda x: str(int(x)))
+def test_more_transforms_bit_identical(reference, typ, dt):
+    from meltw_move_helpers import MoveCase
+    from test_meltw_move_gpu import transform_shapes
+    _pin_whole_allocation(reference, MoveCase(typ, dt, *transform_shapes(typ)[0], off_out=capi.DT_SIZE[dt]))
+
+
+@pytest.mark.parametrize("dt", [DT.F32, DT.BF16, DT.I8])
+@pytest.mark.parametrize("mode", [UNARY_FLAG.GS_COLS, UNARY_FLAG.GS_ROWS, UNARY_FLAG.GS_OFFS])
+@pytest.mark.parametrize("idx8", [0, 1])
+def test_scatter_bit_identical(reference, dt, mode, idx8):
+    """unique indices; the destination is pre-filled: what no index names keeps its bytes on both sides."""
+    from meltw_move_helpers import MoveCase
+    case = MoveCase(UNARY.SCATTER, dt, 37, 9, 39, 41, flags=mode | (UNARY_FLAG.IDX_SIZE_8BYTES if idx8 else UNARY_FLAG.IDX_SIZE_4BYTES), off_out=8)
+    assert np.unique(case.idx).size == case.idx.size
+    _pin_whole_allocation(reference, case)
+
+
+@pytest.mark.parametrize("mode", [UNARY_FLAG.GS_COLS, UNARY_FLAG.GS_ROWS, UNARY_FLAG.GS_OFFS])
+@pytest.mark.parametrize("dt", [DT.F16, DT.F32])
+def test_gather_with_repeated_indices_bit_identical(reference, mode, dt):
+    """an embedding look-up names rows more than once (the F16 rows are the 16-bit branch through another type)"""
+    from meltw_move_helpers import MoveCase
+    case = MoveCase(UNARY.GATHER, dt, 37, 9, 41, 39, flags=mode | UNARY_FLAG.IDX_SIZE_4BYTES, off_out=8)
+    assert np.unique(case.idx).size < case.idx.size
+    _pin_whole_allocation(reference, case)
+    _pin_whole_allocation(reference, MoveCase(UNARY.GATHER, dt, 37, 9, 41, 39, flags=mode | UNARY_FLAG.IDX_SIZE_8BYTES, idx="equal" if mode != UNARY_FLAG.GS_OFFS else "reversed"))
+
+
+def test_reference_moves_no_8_byte_payload(reference):
+    """NOT_PINNED's first entry: the reference leaves the output of an F64 gather as it was."""
+    from meltw_move_helpers import MoveCase
+    case = MoveCase(UNARY.GATHER, DT.F64, 37, 9, 41, 39, flags=UNARY_FLAG.GS_ROWS | UNARY_FLAG.IDX_SIZE_4BYTES)
+    assert np.array_equal(case.run_reference(reference), case.out0)
+    assert all(len(why) > 60 for why in NOT_PINNED.values())
+
+
 @pytest.mark.parametrize("typ", [UNARY.REDUCE_X_OP_ADD, UNARY.REDUCE_X2_OP_ADD, UNARY.REDUCE_X_X2_OP_ADD, UNARY.REDUCE_X_OP_MAX, UNARY.REDUCE_X_OP_MIN, UNARY.REDUCE_X_OP_ABSMAX])
 @pytest.mark.parametrize("rows", [0, 1])
 @pytest.mark.parametrize("in_dt", [DT.F32, DT.BF16])
