@@ -423,7 +423,7 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemm
  * 0 with the handle's refusal code set for an ineligible handle (it serves both forms).  `workspace` must be 16-byte aligned and device-accessible,
  * workspace_bytes at least the query's value; nothing beyond that value is written.
  * Eligible handles: exactly those of libxsmm_hip_gemm_batch_reduce_segments (ADDRESS form) and of libxsmm_hip_gemm_batch_reduce_segments_offsets (OFFSET form,
- * with TRANS_A / TRANS_B under its rules).  Ext handles are refused: a fused epilogue over slices is out of scope.  Errors are set before anything is
+ * with TRANS_A / TRANS_B under its rules).  Ext handles are refused here: they go to the two libxsmm_hip_gemm_ext_batch_reduce_segments*_sliced entries below.  Errors are set before anything is
  * launched, one per refusal.  -2: param, blk_ptr, c_list / c_offs or an OFFSET base is NULL while nblocks > 0; seg_ptr, a_*, b_* or workspace is NULL while
  * nslices > 0; workspace_bytes below the query's value.  -3: every handle refusal of the sibling entry, in its words; a workspace that is not 16-byte
  * aligned.  -4: no device.  nblocks = 0 does nothing.  Follows the thread's launch mode like the siblings (blocking, stream-ordered, coalescing: flushed
@@ -441,6 +441,58 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced(libxsmm_g
   size_t nblocks, const unsigned long long* blk_ptr,
   size_t nslices, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs,
   void* workspace, size_t workspace_bytes);
+
+/* Sliced segments through an ext handle: the two sliced entries above with the fused epilogue of libxsmm_hip_gemm_ext_batch_reduce_segments /
+ * ..._ext_batch_reduce_segments_offsets -- column bias, ReLU (+ bitmask), sigmoid -- applied to the blocks' sums in the second launch.  The call a small-batch
+ * convolution or a skewed block-sparse layer makes: offset lists computed once per geometry, chains cut by the caller, bias and activation fused.
+ *   libxsmm_hip_gemm_ext_batch_reduce_segments_sliced(kernel, param, nblocks, blk_ptr, nslices, seg_ptr, a_list, b_list, c_list, d_list, mask_list,
+ *                                                     workspace, workspace_bytes)
+ *   libxsmm_hip_gemm_ext_batch_reduce_segments_offsets_sliced(kernel, param, nblocks, blk_ptr, nslices, seg_ptr, a_offs, b_offs, c_offs, d_offs, mask_offs,
+ *                                                             workspace, workspace_bytes)
+ * The two-level CSR, the workspace contract and the base / list rules are those of the plain sliced entries.  d_list / d_offs and mask_list / mask_offs hold
+ * NBLOCKS entries and mean what they mean in the unsliced ext entries: d_list == NULL (d_offs == NULL) on a bias handle says that the one bias at
+ * param->d.primary serves every block; the mask list is required exactly when the ReLU carries LIBXSMM_MELTW_FLAG_UNARY_BITMASK_2BYTEMULT and is ignored
+ * otherwise; bias entries need element alignment only, mask entries byte alignment only.  In the OFFSET form the five bases (param->{a,b,c,d}.primary and
+ * param->c.secondary) travel BY VALUE.  Every list is read in place, nothing is staged: both calls can be captured into a graph.
+ * Per C block b:
+ *   partials     P_j = slice j's accumulator chain over (product, k) in list order, started at +0 in f32 -- what the plain sliced entries compute; an empty
+ *                slice gives +0.
+ *   start value  that of the unsliced ext entries: bias[i] (bias, beta = 0); bias[i] + C(i,j) (bias, beta = 1: ONE f32 add of the widened values);
+ *                C(i,j) (beta = 1, no bias); +0 otherwise.
+ *   sum          acc = start; for j ascending over the block's slices acc = acc + P_j, one IEEE f32 add each with denormals kept.
+ *   mask         bit i % 8 of byte i / 8 + j * (mask_ld / 8), mask_ld = ldc rounded up to 16, is !(acc <= 0); written for i < m, j < n only -- every other bit
+ *                and byte of the mask block stays the caller's.
+ *   activation   ReLU (x <= 0 ? +0 : x) or the library's sigmoid, the functions of every fused kernel; then one store with C's ldc and type, with one rounding
+ *                through the library's bf16 conversion for a bf16 C.  Bytes of C outside m x n stay the caller's.
+ *   no slices    the block stores the activation of its start value and the mask taken from it, for EVERY beta: bitwise what the unsliced ext entry stores for a
+ *                segment of count 0.
+ * Consequences: with beta = 0, no bias and one slice per block the result is bitwise the unsliced ext call's for every activation, mask included (a chain
+ * started at +0 never yields -0, so +0 + P is P); with a bias or beta = 1 the start value is ADDED TO the partial sum instead of starting the chain -- the
+ * documented difference, as in the plain sliced entries.  No atomics, no arrival order: the same bits on every run, stream and grid size.  Overlapping C or
+ * mask blocks are undefined; A, B and bias blocks may be shared.
+ *   libxsmm_hip_gemm_ext_batch_reduce_segments_sliced_workspace(kernel, nslices)
+ * is the only authority on the workspace's size for ext handles, with the bounds of the plain query; 0 with the refusal code set for an ineligible handle (an
+ * operator outside the list among them).  The plain query keeps refusing ext handles.
+ * Eligible handles: ADDRESS form, exactly those of libxsmm_hip_gemm_ext_batch_reduce_segments; OFFSET form, exactly those of
+ * libxsmm_hip_gemm_ext_batch_reduce_segments_offsets (NN, TN, NT, TT).  An ext handle WITHOUT operators runs the plain sliced path unchanged and is bit for
+ * bit the plain sliced call on the matching plain handle -- f64 included, and a block without slices under beta = 1 stays untouched; f64 with operators is
+ * refused; plain handles are refused ("not an ext kernel").  Errors are set before anything is launched, one per refusal, with the siblings' codes and words:
+ * -2 for a NULL argument that is needed (as in the plain sliced entries), a workspace below the query's value, a bias handle without a bias source (ADDRESS:
+ * d_list and param->d.primary both NULL; OFFSET: param->d.primary NULL), a bitmask handle without mask_list / mask_offs or, OFFSET, without
+ * param->c.secondary; -3 for every handle refusal and a workspace that is not 16-byte aligned; -4: no device.  nblocks = 0 does nothing.  Follows the thread's
+ * launch mode like the siblings.  A call is TWO launches in order on one stream or pipeline lane (with nslices = 0 the first is skipped);
+ * libxsmm_hip_launch_count counts both; libxsmm_hip_kernel_name(kernel, 1) names the first, the plain sliced entries' kernels, reused as they are; the second
+ * is gemm_segments_slice_reduce_fused_kernel<0> (f32 C) or <1> (bf16 C).  DESIGN.md section 9.6 has the mask scheme and the measurements.
+ */
+LIBXSMM_API size_t libxsmm_hip_gemm_ext_batch_reduce_segments_sliced_workspace(libxsmm_gemmfunction_ext kernel, size_t nslices);
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_sliced(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param,
+  size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list,
+  const void* const* d_list, void* const* mask_list, void* workspace, size_t workspace_bytes);
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets_sliced(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param,
+  size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs,
+  const long long* d_offs, const long long* mask_offs, void* workspace, size_t workspace_bytes);
 
 /* ---- multi-GPU: the batch / packed / N axis is split by contiguous blocks -----------
  * One process per GPU; no collective on the data path.  Rank r of `world` owns

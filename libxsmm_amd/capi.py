@@ -309,6 +309,11 @@ class Api:
                                                            [vp, C.POINTER(GemmParam), C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t])
             self.hip_gemm_batch_reduce_segments_offsets_sliced = f("hip_gemm_batch_reduce_segments_offsets_sliced", None,
                                                                    [vp, C.POINTER(GemmParam), C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t])
+            self.hip_gemm_ext_batch_reduce_segments_sliced_workspace = f("hip_gemm_ext_batch_reduce_segments_sliced_workspace", C.c_size_t, [vp, C.c_size_t])
+            self.hip_gemm_ext_batch_reduce_segments_sliced = f("hip_gemm_ext_batch_reduce_segments_sliced", None,
+                                                               [vp, C.POINTER(GemmExtParam), C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, C.c_size_t])
+            self.hip_gemm_ext_batch_reduce_segments_offsets_sliced = f("hip_gemm_ext_batch_reduce_segments_offsets_sliced", None,
+                                                                       [vp, C.POINTER(GemmExtParam), C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, C.c_size_t])
             self.hip_meltw_unary_batch_strided = f("hip_meltw_unary_batch_strided", None, [vp, C.POINTER(UnaryParam), C.c_size_t, ll, ll, ll])
             self.hip_meltw_binary_batch_strided = f("hip_meltw_binary_batch_strided", None, [vp, C.POINTER(BinaryParam), C.c_size_t, ll, ll, ll])
             self.hip_meltw_ternary_batch_strided = f("hip_meltw_ternary_batch_strided", None, [vp, C.POINTER(TernaryParam), C.c_size_t, ll, ll, ll, ll])

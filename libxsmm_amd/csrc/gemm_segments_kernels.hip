@@ -29,6 +29,8 @@
 // than the ADDRESS kernels' 160 / 196 / 72 -- the register allocator does not keep the four bodies apart (DESIGN.md section 9.2 has the numbers).
 // The two *_sliced entries (further down) let the CALLER cut a chain: pass 1 is the same item loop over (slice, tile) with the partials
 // of a workspace as destinations, pass 2 adds a block's partials in ascending slice order.  The entries above never split a segment.
+// The two ext *_sliced entries are the same two passes with the FusedEpilogue's operators applied to the blocks' sums in pass 2
+// (gemm_segments_slice_reduce_fused_kernel); pass 1 is launched exactly as for the plain handles.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "internal.hpp"
@@ -265,6 +267,205 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSli
   }
 }
 
+// ---- pass 2 with the ext ABI's epilogue (libxsmm_hip_gemm_ext_batch_reduce_segments_sliced, ..._offsets_sliced) ------------------------------------------
+// acc = start value of the unsliced ext entries (bias, bias + C in one f32 add, C or +0: acc_start in gemm_group_tile.hpp), then acc += P_j in ascending slice
+// order as above, then the mask bit !(acc <= 0), then act_fixed<1> / act_fixed<3>, then the store of pass 2.  A block without slices is NOT skipped: it stores
+// the activation of its start value and the mask taken from it, for every beta -- what the unsliced ext entry stores for a segment of count 0.  CLS: 0 f32 C,
+// 1 bf16 C (the bias has C's type).  The bias and mask entries of block b are wave-uniform scalar loads like C's entry.  No LDS, no scratch, vector stores only.
+// Who writes a mask byte.  A byte holds 8 rows of ONE column; every byte is written by exactly one lane with one store, and no byte is ever read-merge-written by
+// two lanes.  Two ways of handing out the work, chosen by a wave-uniform test of the kernel arguments:
+//   runs   (no bitmask, or m % 8 == 0)  the work items of the plain kernel: lane l owns 4 consecutive elements of the dense partial, 16-byte loads.  With a
+//          bitmask m % 8 == 0, so a column starts at a multiple of 8 dense elements, a byte is the 8 elements of the lane pair (2 l, 2 l + 1) -- never cut by the
+//          end of a run (256 elements) -- and all its rows are valid: the odd lane's four predicate bits reach the even lane through one DPP quad permute, the
+//          even lane stores the whole byte.  Nothing is read.  The bias: a lane's rows are 4 consecutive entries of the m-vector when m % 4 == 0 -- one vector
+//          load when the bias pointer allows (wave-uniform), else element by element.
+//   bytes  (bitmask and m % 8 != 0)     an element run's end can fall inside a byte, so the runs are not used: the unit of work is a MASK BYTE -- (column j,
+//          rows 8 q .. min(8 q + 8, m) - 1), n * ceil(m / 8) units per block -- and lane l of item (block, run) owns the units run * 64 + l, + runs * 64, ...
+//          A unit's elements are consecutive in the dense partial but not 16-byte aligned: element loads, four slices in flight as above.  The lane owns all bits
+//          of its byte: a whole-byte store when 8 rows are valid, read-merge-write of the column's last byte by that one lane -- no other lane or wave touches it.
+template <int CLS> __device__ __forceinline__ float slice_c_load(const GM void* p, long long i) {
+  if constexpr (CLS == 1) return bf16_bits_to_f32(((GM const unsigned short*)p)[i]); else return ((GM const float*)p)[i];
+}
+
+template <int CLS>
+__device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q, const GemmSliceEpilogue& e, gptr c, gcptr d, GM unsigned char* mask, gcptr ws0,
+  unsigned long long ns, unsigned int run, unsigned int lane) {
+  typedef typename std::conditional<CLS == 1, unsigned short, float>::type c_t;
+  constexpr int V = 4;
+  typedef c_t cvec_t __attribute__((ext_vector_type(V)));
+  const unsigned int m = (unsigned int)q.m, mn = m * (unsigned int)q.n;
+  const unsigned int e0 = (run * 64u + lane) * (unsigned int)V;
+  const bool live = e0 < mn;
+  const unsigned int el = live ? e0 : 0u;                                        // lanes past the block re-read its first elements and store nothing
+  const unsigned int j0 = el / m, i0 = el - j0 * m;
+  const bool wide = q.wide_ld && ((unsigned int)(size_t)c & (unsigned int)(V * sizeof(c_t) - 1)) == 0;
+  GM c_t* cw = (GM c_t*)c + ((long long)j0 * q.ldc + i0);
+  f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (q.beta1) {
+    if (wide) {
+      const cvec_t x = *(GM const cvec_t*)cw;
+#pragma unroll
+      for (int v = 0; v < V; ++v) { if constexpr (CLS == 1) acc[v] = bf16_bits_to_f32(x[v]); else acc[v] = x[v]; }
+    } else {
+      unsigned int i = i0, j = j0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        if (live && e0 + v < mn) acc[v] = slice_c_load<CLS>(c, (long long)j * q.ldc + i);
+        if (++i == m) { i = 0; ++j; }
+      }
+    }
+  }
+  if (e.colbias) {                                                               // bias, or bias + C in one f32 add
+    f32x4 bv;
+    if ((m & 3u) == 0 && ((unsigned int)(size_t)d & (unsigned int)(V * sizeof(c_t) - 1)) == 0) {
+      const cvec_t x = *(GM const cvec_t*)((GM const c_t*)d + i0);
+#pragma unroll
+      for (int v = 0; v < V; ++v) { if constexpr (CLS == 1) bv[v] = bf16_bits_to_f32(x[v]); else bv[v] = x[v]; }
+    } else {
+      unsigned int i = i0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) { bv[v] = slice_c_load<CLS>(d, i); if (++i == m) i = 0; }
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = q.beta1 ? bv[v] + acc[v] : bv[v];
+  }
+  gcptr p = ws0 + (long long)el * 4;
+  unsigned long long s = 0;
+  for (; s + 4 <= ns; s += 4) {
+    const f32x4 x0 = *(GM const f32x4*)p, x1 = *(GM const f32x4*)(p + q.pstride), x2 = *(GM const f32x4*)(p + 2 * q.pstride), x3 = *(GM const f32x4*)(p + 3 * q.pstride);
+    p += 4 * q.pstride;
+    acc += x0; acc += x1; acc += x2; acc += x3;
+  }
+  for (; s < ns; ++s) { acc += *(GM const f32x4*)p; p += q.pstride; }
+  if (e.act == 2) {                                                              // m % 8 == 0: the lane pair's byte, all 8 rows valid (every lane is active here)
+    unsigned int nib = 0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) nib |= (acc[v] <= 0.0f ? 0u : 1u) << v;
+    const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)nib, 0xB1, 0xf, 0xf, false);   // quad_perm [1, 0, 3, 2]: the pair's other lane
+    if (live && (lane & 1u) == 0) mask[(long long)(i0 >> 3) + (long long)j0 * (e.mask_ld >> 3)] = (unsigned char)(nib | (hi << 4));
+  }
+  if (e.act == 3) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = act_fixed<3>(acc[v]);
+  } else if (e.act != 0) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = act_fixed<1>(acc[v]);
+  }
+  if (!live) return;
+  if constexpr (CLS == 1) {
+    float x[V]; unsigned int pk[V / 2];
+#pragma unroll
+    for (int v = 0; v < V; ++v) x[v] = acc[v];
+    bf16_pk_exact_n<V / 2>(x, pk);
+    if (wide) { u32x2 w = {pk[0], pk[1]}; *(GM u32x2*)cw = w; }
+    else {
+      unsigned int i = i0, j = j0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        if (e0 + v < mn) ((GM unsigned short*)c)[(long long)j * q.ldc + i] = (unsigned short)((v & 1) ? (pk[v / 2] >> 16) : (pk[v / 2] & 0xffffu));
+        if (++i == m) { i = 0; ++j; }
+      }
+    }
+  } else if (wide) *(GM f32x4*)cw = acc;
+  else {
+    unsigned int i = i0, j = j0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      if (e0 + v < mn) ((GM float*)c)[(long long)j * q.ldc + i] = acc[v];
+      if (++i == m) { i = 0; ++j; }
+    }
+  }
+}
+
+template <int CLS>
+__device__ __forceinline__ void slice_reduce_fused_bytes(const GemmSliceReduce& q, const GemmSliceEpilogue& e, gptr c, gcptr d, GM unsigned char* mask, gcptr ws0,
+  unsigned long long ns, unsigned int run, unsigned int lane) {
+  typedef typename std::conditional<CLS == 1, unsigned short, float>::type c_t;
+  const unsigned int m = (unsigned int)q.m, mq = (m + 7u) >> 3, units = mq * (unsigned int)q.n;
+  for (unsigned int u0 = run * 64u; u0 < units; u0 += q.runs * 64u) {
+    const bool live = u0 + lane < units;
+    const unsigned int u = live ? u0 + lane : 0u;                                // lanes past the block re-read its first unit and store nothing
+    const unsigned int j = u / mq, qi = u - j * mq, i0 = qi * 8u;
+    const unsigned int nv = min(8u, m - i0);                                     // valid rows of the byte
+    GM c_t* cc = (GM c_t*)c + ((long long)j * q.ldc + i0);
+    float acc[8];
+#pragma unroll
+    for (int v = 0; v < 8; ++v) acc[v] = 0.0f;
+    if (q.beta1) {
+#pragma unroll
+      for (int v = 0; v < 8; ++v) if ((unsigned int)v < nv) acc[v] = slice_c_load<CLS>(cc, v);
+    }
+    if (e.colbias) {
+#pragma unroll
+      for (int v = 0; v < 8; ++v) if ((unsigned int)v < nv) { const float bv = slice_c_load<CLS>(d, i0 + v); acc[v] = q.beta1 ? bv + acc[v] : bv; }
+    }
+    gcptr p = ws0 + ((long long)j * m + i0) * 4;
+    unsigned long long s = 0;
+    for (; s + 4 <= ns; s += 4) {
+      float x[4][8];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int v = 0; v < 8; ++v) x[t][v] = (unsigned int)v < nv ? ((GM const float*)(p + t * q.pstride))[v] : 0.0f;
+      }
+      p += 4 * q.pstride;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int v = 0; v < 8; ++v) acc[v] += x[t][v];
+      }
+    }
+    for (; s < ns; ++s) {
+      float x[8];
+#pragma unroll
+      for (int v = 0; v < 8; ++v) x[v] = (unsigned int)v < nv ? ((GM const float*)p)[v] : 0.0f;
+      p += q.pstride;
+#pragma unroll
+      for (int v = 0; v < 8; ++v) acc[v] += x[v];
+    }
+    unsigned int bits = 0;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) bits |= ((unsigned int)v < nv && !(acc[v] <= 0.0f) ? 1u : 0u) << v;
+    if (live) {                                                                  // this lane alone owns the byte
+      GM unsigned char* byte = mask + qi + (long long)j * (e.mask_ld >> 3);
+      const unsigned int vm = (1u << nv) - 1u;
+      *byte = nv == 8u ? (unsigned char)bits : (unsigned char)((*byte & ~vm) | bits);
+    }
+#pragma unroll
+    for (int v = 0; v < 8; ++v) acc[v] = act_fixed<1>(acc[v]);
+    if constexpr (CLS == 1) {
+      unsigned int pk[4];
+      bf16_pk_exact_n<4>(acc, pk);
+#pragma unroll
+      for (int v = 0; v < 8; ++v) if (live && (unsigned int)v < nv) ((GM unsigned short*)cc)[v] = (unsigned short)((v & 1) ? (pk[v / 2] >> 16) : (pk[v / 2] & 0xffffu));
+    } else {
+#pragma unroll
+      for (int v = 0; v < 8; ++v) if (live && (unsigned int)v < nv) ((GM float*)cc)[v] = acc[v];
+    }
+  }
+}
+
+template <int CLS>
+__global__ __launch_bounds__(256) void gemm_segments_slice_reduce_fused_kernel(GemmSliceReduce q, GemmSliceEpilogue e, unsigned long long total) {
+  const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned int lane = threadIdx.x & 63u;
+  const unsigned long long step = (unsigned long long)gridDim.x * 4u;
+  const bool bytes = e.act == 2 && (q.m & 7) != 0;
+  for (unsigned long long item = (unsigned long long)blockIdx.x * 4u + wave; item < total; item += step) {
+    unsigned long long b = item; unsigned int run = 0;
+    if (q.runs != 1) { b = item / q.runs; run = (unsigned int)(item - b * q.runs); }
+    const unsigned long long s0 = uniform_u64(((GM const unsigned long long*)q.blk_ptr)[b]), s1 = uniform_u64(((GM const unsigned long long*)q.blk_ptr)[b + 1]);
+    gptr c = q.c_base ? (gptr)q.c_base + (long long)uniform_u64(((GM const unsigned long long*)q.c_list)[b]) : (gptr)list_entry(q.c_list, b);
+    gcptr d = (gcptr)e.d;
+    if (e.colbias && e.d_list) d = e.offs ? d + (long long)uniform_u64(((GM const unsigned long long*)e.d_list)[b]) : list_entry(e.d_list, b);
+    GM unsigned char* mask = nullptr;
+    if (e.act == 2) mask = e.offs ? (GM unsigned char*)e.mask + (long long)uniform_u64(((GM const unsigned long long*)e.mask_list)[b]) : (GM unsigned char*)list_entry(e.mask_list, b);
+    gcptr ws0 = (gcptr)q.ws + (long long)s0 * q.pstride;
+    if (bytes) slice_reduce_fused_bytes<CLS>(q, e, c, d, mask, ws0, s1 - s0, run, lane);
+    else slice_reduce_fused_run<CLS>(q, e, c, d, mask, ws0, s1 - s0, run, lane);
+  }
+}
+
 // the four instances of an offsets kernel, indexed by forms & 3 (bit 0 TRANS_A, bit 1 TRANS_B)
 #define XAMD_FORMS(NAME) {NAME "<0,0>", NAME "<1,0>", NAME "<0,1>", NAME "<1,1>"}
 static const char* const kSlicedNames[3] = {"gemm_segments_sliced_f32_kernel", "gemm_segments_sliced_bf16_kernel", "gemm_segments_sliced_f64_kernel"};
@@ -341,6 +542,19 @@ static int launch_sliced(const SegmentsLaunch& l, hipStream_t st, const char** k
   q.wide_ld = (l.g.m % V == 0 && l.g.ldc % V == 0) ? 1 : 0;      // a lane's V elements as one load / store of C: inside one column, V-element aligned
   const unsigned long long total = l.nblocks * q.runs;
   const unsigned int grid = group_grid(total);
+  if (l.fused) {                                         // the ext entries: the block-level epilogue lists travel next to q
+    GemmSliceEpilogue e = {};
+    if (l.offsets) {
+      const GemmSegOffsEpilogue& o = *(const GemmSegOffsEpilogue*)l.epilogue;
+      e.d_list = o.d_offs; e.d = o.d; e.mask_list = o.mask_offs; e.mask = o.mask; e.colbias = o.colbias; e.act = o.act; e.mask_ld = o.mask_ld; e.offs = 1;
+    } else {
+      const GemmSegEpilogue& o = *(const GemmSegEpilogue*)l.epilogue;
+      e.d_list = o.d_list; e.d = o.d; e.mask_list = o.mask_list; e.colbias = o.colbias; e.act = o.act; e.mask_ld = o.mask_ld;
+    }
+    if (l.g.c_bf16) hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<1>, dim3(grid), dim3(256), 0, st, q, e, total);
+    else hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<0>, dim3(grid), dim3(256), 0, st, q, e, total);
+    return (int)hipGetLastError();
+  }
   if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<2>, dim3(grid), dim3(256), 0, st, q, total);
   else if (l.g.c_bf16) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<1>, dim3(grid), dim3(256), 0, st, q, total);
   else hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<0>, dim3(grid), dim3(256), 0, st, q, total);

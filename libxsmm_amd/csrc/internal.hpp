@@ -341,6 +341,16 @@ struct GemmSliceReduce {
   unsigned int runs;                                // work items of one block: runs of 64 lanes x 16 bytes of accumulators
   int wide_ld;                                      // m and ldc are multiples of the elements in 16 bytes of accumulators: a lane's run lies in one column of C
 };
+// the fused epilogue of pass 2 (gemm_segments_slice_reduce_fused_kernel: the two libxsmm_hip_gemm_ext_batch_reduce_segments*_sliced entries), by value next to the
+// GemmSliceReduce: GemmSegEpilogue / GemmSegOffsEpilogue with one entry per BLOCK
+struct GemmSliceEpilogue {
+  const void* d_list;                               // nblocks pointers, or (offs) signed byte offsets from `d`; NULL: `d` is shared by every block
+  const char* d;
+  const void* mask_list;                            // nblocks pointers, or (offs) signed byte offsets from `mask` (act == 2)
+  char* mask;
+  int colbias, act, mask_ld;                        // as in GemmSegEpilogue
+  int offs;
+};
 // bytes between the partials of a sliced call: m x n accumulators (f64 for class 2, else f32), rounded up to 16
 inline unsigned long long slice_partial_stride(unsigned long long mn, int cls) { return (mn * (cls == 2 ? 8u : 4u) + 15u) & ~15ull; }
 inline unsigned int slice_reduce_runs(unsigned long long mn, int cls) { const unsigned int per = cls == 2 ? 128u : 256u; return (unsigned int)((mn + per - 1) / per); }

@@ -2618,7 +2618,7 @@ static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, 
   const bool is_ext = (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI) != 0;
   if (!ext && is_ext) { set_error(-3, "%s: ext handles are not taken", fn); return nullptr; }
   if (ext && !is_ext) {
-    set_error(-3, "%s: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_reduce_segments%s)", fn, offsets ? "_offsets" : ""); return nullptr;
+    set_error(-3, "%s: handle is not an ext kernel (libxsmm_dispatch_brgemm_ext; plain handles go to libxsmm_hip_gemm_batch_reduce_segments%s%s)", fn, offsets ? "_offsets" : "", sl ? "_sliced" : ""); return nullptr;
   }
   if (offsets && !(d.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET)) {
     set_error(-3, "%s: handle is not an OFFSET batch-reduce kernel (%s with LIBXSMM_GEMM_BATCH_REDUCE_OFFSET)", fn, ext ? "libxsmm_dispatch_brgemm_ext" : "libxsmm_dispatch_brgemm"); return nullptr;
@@ -2688,7 +2688,7 @@ static void run_segments(const char* fn, bool ext, bool offsets, const void* ker
     l.pstride = (long long)slice_partial_stride((unsigned long long)k->g.m * k->g.n, l.cls);
     const size_t need = nsegments * (size_t)l.pstride;
     if (sl->workspace_bytes < need) {
-      set_error(-2, "%s: workspace_bytes = %zu is below the %zu bytes that libxsmm_hip_gemm_batch_reduce_segments_sliced_workspace(kernel, %zu) asks for", fn, sl->workspace_bytes, need, nsegments); return;
+      set_error(-2, "%s: workspace_bytes = %zu is below the %zu bytes that libxsmm_hip_gemm_%sbatch_reduce_segments_sliced_workspace(kernel, %zu) asks for", fn, sl->workspace_bytes, need, ext ? "ext_" : "", nsegments); return;
     }
     if (((size_t)sl->workspace & 15u) != 0) { set_error(-3, "%s: workspace is not 16-byte aligned", fn); return; }
   }
@@ -2774,6 +2774,31 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced(libxsmm_g
   size_t nslices, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs, void* workspace, size_t workspace_bytes) {
   const SegmentsSliced sl = {nblocks, blk_ptr, workspace, workspace_bytes};
   run_segments("libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced", false, true, (const void*)kernel, param, nslices, seg_ptr, a_offs, b_offs, c_offs, nullptr, nullptr, &sl);
+}
+// The sliced forms of the two ext entries: the same two launches, with the handle's epilogue applied to the blocks' sums in pass 2
+// (gemm_segments_slice_reduce_fused_kernel).  d_list / mask_list (d_offs / mask_offs) hold one entry per BLOCK.  An ext handle without operators runs the plain
+// sliced path.
+LIBXSMM_API size_t libxsmm_hip_gemm_ext_batch_reduce_segments_sliced_workspace(libxsmm_gemmfunction_ext kernel, size_t nslices) {
+  const char* fn = "libxsmm_hip_gemm_ext_batch_reduce_segments_sliced_workspace";
+  const KernelCtx* peek = ctx_from_handle((const void*)kernel);
+  const bool offsets = peek && peek->kind == K_GEMM && (peek->g.flags & LIBXSMM_GEMM_FLAG_BATCH_REDUCE_OFFSET) != 0;   // either form's handles; every other handle gets the ADDRESS entry's words
+  GemmGroupDesc g; int cls = 0, forms = 0, colbias = 0, act = 0; unsigned long long tiles = 0;
+  const SegmentsSliced sl = {1, nullptr, nullptr, 0};
+  const KernelCtx* k = segments_handle(fn, true, (const void*)kernel, nullptr, nslices, g, cls, tiles, offsets ? &forms : nullptr, &sl);
+  if (!k || !segments_operators(fn, k->g, cls, colbias, act) || tiles == 0) return 0;
+  return nslices * (size_t)slice_partial_stride((unsigned long long)k->g.m * k->g.n, cls);
+}
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_sliced(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param, size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list, const void* const* d_list, void* const* mask_list,
+  void* workspace, size_t workspace_bytes) {
+  const SegmentsSliced sl = {nblocks, blk_ptr, workspace, workspace_bytes};
+  run_segments("libxsmm_hip_gemm_ext_batch_reduce_segments_sliced", true, false, (const void*)kernel, param, nslices, seg_ptr, a_list, b_list, c_list, d_list, mask_list, &sl);
+}
+LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets_sliced(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param, size_t nblocks, const unsigned long long* blk_ptr,
+  size_t nslices, const unsigned long long* seg_ptr, const long long* a_offs, const long long* b_offs, const long long* c_offs, const long long* d_offs, const long long* mask_offs,
+  void* workspace, size_t workspace_bytes) {
+  const SegmentsSliced sl = {nblocks, blk_ptr, workspace, workspace_bytes};
+  run_segments("libxsmm_hip_gemm_ext_batch_reduce_segments_offsets_sliced", true, true, (const void*)kernel, param, nslices, seg_ptr, a_offs, b_offs, c_offs, d_offs, mask_offs, &sl);
 }
 // ---- multi-device launch from ONE host thread (the reference's scale-out axis is the caller's loop,
 // samples/xgemm/gemm_kernel.c:4063-4066) --------------------------------------------------------------------------------------------------------
