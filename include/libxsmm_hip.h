@@ -291,13 +291,20 @@ LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan
  * result is the k-ordered fmaf chain bit for bit.  A segment of count 0 is the reference's call with a count of 0: beta = 0 sets the m x n block to +0,
  * beta = 1 leaves it untouched.  Work is handed to the device in list order (a work item is a segment's C tile, taken up in ascending order): a caller who
  * lists long segments first gets longest-first scheduling for free; a segment is never split, which would reorder its sum.
- * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16; A flat (or VNNI_A for bf16), B flat, C not VNNI, no transposes; beta 0
- * or 1; no flag beyond those and the hints; any m, n, k and leading dimensions whose element offsets inside an operand stay below 2^31.  Block pointers
- * need element alignment only.  Follows the thread's launch mode: blocking (returns when done), stream-ordered, coalescing (the queue is flushed first),
+ * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16, BF8 x BF8 -> f32 / BF8, HF8 x HF8 -> f32 / HF8 (comp f32); A flat (or
+ * VNNI_A for bf16; for the 8-bit floats VNNI_A is required: A is taken as VNNI-4 only, A(i,k) at ((k / 4) * lda + i) * 4 + k % 4, k a multiple of 4), B flat,
+ * C not VNNI, no transposes; beta 0 or 1; no flag beyond those and the hints; any m, n, k and leading dimensions whose element offsets inside an operand stay
+ * below 2^31.  Block pointers need element alignment only (8-bit floats: any byte).
+ * 8-bit floats (BF8 = E5M2, HF8 = E4M3) [ref: src/generator_gemm_reference_impl.c:2420-2510, own-type C :2511-2619]: per segment one f32 accumulator over
+ * (product, k) in list order, started at +0 (beta = 0) or at C (beta = 1; an 8-bit C is widened to f32); an f32 C is stored as it is, an 8-bit C leaves through
+ * the library's two-step conversion f32 -> f16 -> 8 bits, NaNs in software -- the conversion the dense 8-bit float kernels store with.  A count of 0 stores
+ * beta * C (for an 8-bit C the round trip of the byte: the identity on every code that is not a NaN).  Bytes of C outside m x n stay the caller's.  The matrix
+ * core (v_mfma_f32_32x32x16_{bf8_bf8,fp8_fp8}, v_mfma_f32_16x16x32_*) aligns the products of one instruction before it adds them, so the result is the
+ * reference's serial chain within a tolerance -- bitwise where every partial sum is exact -- like the dense 8-bit float kernels.  Follows the thread's launch mode: blocking (returns when done), stream-ordered, coalescing (the queue is flushed first),
  * inside a pipeline section (the launch goes to a lane).  Errors are set before anything is launched.  -2: param, seg_ptr, a_list, b_list or c_list is NULL
  * while nsegments > 0; -3: an unknown handle, a TPP / equation / sparse / ext handle, a GEMM handle that is not ADDRESS batch-reduce, or a type, layout or
  * flag outside the list above (the message names which); -4: no device.  nsegments = 0 does nothing.  libxsmm_hip_kernel_name(kernel, 1) names the
- * kernel that ran (gemm_segments_f32_kernel, _f64_kernel, _bf16_kernel).
+ * kernel that ran (gemm_segments_f32_kernel, _f64_kernel, _bf16_kernel, _bf8_kernel, _hf8_kernel).
  */
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
   size_t nsegments, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list);
@@ -320,8 +327,9 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction ker
  * count of 0: it stores the activation of the start value (the bias, bias + C, C or +0) and the mask taken from it.
  * Eligible handles: ADDRESS batch-reduce ext handles under the plain entry's type, layout and flag rules (f32 -> f32, bf16 -> f32 / bf16; A flat or VNNI-2,
  * B flat, C not VNNI, NN; beta 0 or 1; the hints; element offsets below 2^31) with BINARY_ADD + BCAST_COL_IN_0/1, cp RELU (with or without bitmask), cp
- * SIGMOID, or no operator at all -- an ext handle without operators is taken for f64 as well and runs the plain kernels.  Errors are set before anything is
- * launched.  -2: param, seg_ptr, a_list, b_list or c_list is NULL while nsegments > 0; a bias handle with d_list and param->d.primary both NULL; a bitmask
+ * SIGMOID, or no operator at all -- an ext handle without operators is taken for f64 and for the 8-bit floats (BF8 / HF8 -> f32 / own type, A VNNI-4) as well
+ * and runs the plain kernels; an 8-bit float ext handle with a bias or an activation is refused ("taken without operators only").  Errors are set before
+ * anything is launched.  -2: param, seg_ptr, a_list, b_list or c_list is NULL while nsegments > 0; a bias handle with d_list and param->d.primary both NULL; a bitmask
  * handle with mask_list NULL.  -3: an unknown handle, a non-ext / TPP / equation / sparse handle, a handle that is not ADDRESS batch-reduce, a type, layout,
  * flag or operator outside the list (the message names which).  -4: no device.  nsegments = 0 does nothing.  Follows the thread's launch mode like the plain
  * entry.  libxsmm_hip_kernel_name(kernel, 1) names the kernel that ran (gemm_segments_f32_fused_kernel, gemm_segments_bf16_fused_kernel; without operators
@@ -347,14 +355,16 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction
  * are undefined; A and B blocks may be shared freely.  Order, start value and count 0 are those of libxsmm_hip_gemm_batch_reduce_segments: one accumulator
  * chain over (product, k) in list order from C (beta = 1) or +0; a segment of count 0 stores beta * C; for f32 the result is the k-ordered fmaf chain bit for
  * bit, in every form.  Work is handed out in list order; a segment is never split.
- * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16.  A flat, A with TRANS_A (flat, A(i,k) at i * lda + k, lda >= k) or, for
+ * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16; BF8 x BF8 -> f32 / BF8 and HF8 x HF8 -> f32 / HF8 NN only, A VNNI-4
+ * (LIBXSMM_GEMM_FLAG_VNNI_A required, TRANS_A / TRANS_B refused), with the semantics given at libxsmm_hip_gemm_batch_reduce_segments.  A flat, A with TRANS_A (flat, A(i,k) at i * lda + k, lda >= k) or, for
  * bf16, VNNI-2 without TRANS_A; B flat or B with TRANS_B (flat, B(k,j) at k * ldb + j, ldb >= n); both transposes together are allowed; VNNI_B and VNNI_C are
  * refused; beta 0 or 1; no flag beyond those and the hints; element offsets inside one operand (lda * m and ldb * k for transposed ones) stay below 2^31.
  * Offsets need element alignment only.  Follows the thread's launch mode: blocking, stream-ordered, coalescing (the queue is flushed first), inside a pipeline
  * section.  Errors are set before anything is launched, one per refusal.  -2: param, seg_ptr, a_offs, b_offs, c_offs or one of the three bases is NULL while
  * nsegments > 0; -3: an unknown handle, a TPP / equation / sparse / ext handle, a GEMM handle that is not OFFSET batch-reduce, or a type, layout or flag
  * outside the list above (the message names which); -4: no device.  nsegments = 0 does nothing.  libxsmm_hip_kernel_name(kernel, 1) names the kernel that
- * ran (gemm_segments_offs_f32_kernel<ta,tb>, _f64_kernel<ta,tb>, _bf16_kernel<ta,tb>: one instance per pair of transposes).  The two ADDRESS entries above keep refusing transposed operands; ext handles go to
+ * ran (gemm_segments_offs_f32_kernel<ta,tb>, _f64_kernel<ta,tb>, _bf16_kernel<ta,tb>: one instance per pair of transposes; gemm_segments_offs_bf8_kernel<0,0>,
+ * gemm_segments_offs_hf8_kernel<0,0>).  The two ADDRESS entries above keep refusing transposed operands; ext handles go to
  * libxsmm_hip_gemm_ext_batch_reduce_segments_offsets below.
  */
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
@@ -386,7 +396,8 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunc
  * Eligible handles: every handle the plain offsets entry takes, made into an ext handle -- f32 -> f32, bf16 -> f32 / bf16; A flat, TRANS_A or (bf16, without
  * TRANS_A) VNNI-2; B flat or TRANS_B; NN, TN, NT and TT; beta 0 or 1; the hints; element offsets below 2^31 -- with BINARY_ADD + BCAST_COL_IN_0/1, cp RELU (with
  * or without bitmask), cp SIGMOID, or no operator at all: an ext handle without operators is taken for f64 as well and runs the plain offsets kernels; f64 with
- * operators is refused.  Errors are set before anything is launched, one per refusal.  -2: param, seg_ptr, a_offs, b_offs, c_offs or one of the three bases is
+ * operators is refused; the same holds for the 8-bit floats (NN, A VNNI-4: without operators the plain offsets kernels, with operators refused).  Errors are
+ * set before anything is launched, one per refusal.  -2: param, seg_ptr, a_offs, b_offs, c_offs or one of the three bases is
  * NULL while nsegments > 0; a bias handle with param->d.primary NULL; a bitmask handle with mask_offs or param->c.secondary NULL.  -3: an unknown handle, a
  * non-ext / TPP / equation / sparse handle, a handle that is not OFFSET batch-reduce, a type, layout, flag or operator outside the list (the message names
  * which).  -4: no device.  nsegments = 0 does nothing.  Follows the thread's launch mode like its siblings: blocking, stream-ordered, coalescing (the queue is
@@ -411,6 +422,8 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemm
  * handles, f64 for f64) -- for f32 the k-ordered fmaf chain bit for bit, in every transpose form; an empty slice gives +0.  acc = C(i,j) widened to the
  * accumulator type (beta = 1) or +0 (beta = 0); for j ascending over the block's slices acc = acc + P_j, each one IEEE add in the accumulator type with
  * denormals kept; acc is stored with one rounding through the library's bf16 conversion for a bf16 C.  Bytes of the C block outside m x n stay the caller's.
+ * 8-bit float handles (BF8 / HF8, A VNNI-4, NN): the partials are f32, started at +0; pass 2 adds them in ascending slice order to C widened to f32 or to +0
+ * and stores once -- an f32 C as it is, an 8-bit C through the two-step conversion of the unsliced entries; the workspace holds 4-byte accumulators.
  * A block with no slices: beta = 0 stores +0, beta = 1 leaves the block untouched.  Consequences: with beta = 0 and one slice per block the result is bitwise
  * the unsliced call's (a chain started at +0 never yields -0, so +0 + P is P); with beta = 1 the original C is ADDED TO the first partial, not used as the
  * chain's start -- the documented difference from the unsliced entries, as in ORDER_ANY.  Blocks whose C overlaps are undefined; A and B blocks may be shared.
@@ -429,8 +442,9 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemm
  * aligned.  -4: no device.  nblocks = 0 does nothing.  Follows the thread's launch mode like the siblings (blocking, stream-ordered, coalescing: flushed
  * first, pipeline section).  A call is TWO kernel launches in order on the same stream or the same pipeline lane -- the slices' partials, then the blocks'
  * sums (gemm_segments_slice_reduce_kernel<cls>); with nslices = 0 the first is skipped.  libxsmm_hip_launch_count counts both;
- * libxsmm_hip_kernel_name(kernel, 1) names the first (gemm_segments_sliced_f32_kernel, _bf16_kernel, _f64_kernel;
- * gemm_segments_offs_sliced_f32_kernel<ta,tb>, _bf16_kernel<ta,tb>, _f64_kernel<ta,tb>).
+ * libxsmm_hip_kernel_name(kernel, 1) names the first (gemm_segments_sliced_f32_kernel, _bf16_kernel, _f64_kernel, _bf8_kernel, _hf8_kernel;
+ * gemm_segments_offs_sliced_f32_kernel<ta,tb>, _bf16_kernel<ta,tb>, _f64_kernel<ta,tb>, gemm_segments_offs_sliced_bf8_kernel<0,0>, _hf8_kernel<0,0>); the
+ * second is gemm_segments_slice_reduce_kernel<0> for an f32 C, <1> bf16, <2> f64, <3> BF8, <4> HF8.
  */
 LIBXSMM_API size_t libxsmm_hip_gemm_batch_reduce_segments_sliced_workspace(libxsmm_gemmfunction kernel, size_t nslices);
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_sliced(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,

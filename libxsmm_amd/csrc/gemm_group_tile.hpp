@@ -13,6 +13,9 @@
 //         (cdna_hip_programming.md, "FP32-input MFMA"), which is what oracle_gemm_f32_fma computes [ref: src/generator_gemm_reference_impl.c:1359-1426].
 //   bf16: v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x16_bf16, A flat or VNNI-2, B flat, C f32 or bf16 (bf16_cvt.hpp: the reference's conversion exactly).
 //   f64 : v_mfma_f64_16x16x4_f64, T = 16 only, k in natural order, four k per instruction [ref: src/generator_gemm_reference_impl.c:1322-1358].
+//   fp8 : v_mfma_f32_32x32x16_{bf8_bf8,fp8_fp8} / v_mfma_f32_16x16x32_{bf8_bf8,fp8_fp8} (BF8 = E5M2, HF8 = E4M3), A VNNI-4, B flat, NN only, C f32 or the
+//         operands' type (gemm_8bit.hpp: the reference's two-step rounding) [ref: src/generator_gemm_reference_impl.c:2420-2619].  The matrix core aligns the
+//         products of one instruction before it adds them: the reference's serial chain within a tolerance, bitwise where every partial sum is exact.
 // beta = 1 starts the chain at C.  Ragged k is padded with A = -0.0 and B = +0.0: adding the product -0 is an exact identity for every accumulator
 // (+0 + -0 = +0 under round-to-nearest), so the f32 chain stays bitwise.  Rows and columns beyond m / n load the last valid row / column and are never
 // stored, so no access leaves the caller's operands.
@@ -30,7 +33,8 @@
 #include "internal.hpp"
 #include "gemm_device.hpp"
 #include "bf16_cvt.hpp"
-#include "gemm_tile.hpp"                           // act_fixed: the fused activations
+#include "gemm_tile.hpp"                           // act_fixed: the fused activations; bf8_to_f32 / hf8_to_f32
+#include "gemm_8bit.hpp"                           // f32x2_to_fp8_ref: the store of an 8-bit float C
 
 namespace xamd {
 namespace group_tile {
@@ -91,7 +95,6 @@ template <int T> __device__ __forceinline__ int acc_col(int r, unsigned int lane
 }
 
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 template <int T> struct Acc;
@@ -115,8 +118,9 @@ struct FusedEpilogue {
   int colbias, act, mask_ld;                       // act: 0 none, 1 ReLU, 2 ReLU + bitmask, 3 sigmoid (gemm_tile.hpp: act_fixed)
 };
 
-// the accumulator's start value: C (beta = 1) or +0; fused: bias, or bias + C in one f32 add
-template <int T, typename Epi = NoEpilogue>
+// the accumulator's start value: C (beta = 1) or +0; fused: bias, or bias + C in one f32 add.  C8 (the 8-bit float tiles only: 1 BF8, 2 HF8): C is f32 or,
+// with g.c_kind >= 2, of the operands' type and widened; the other instances know c_kind as 0 or 1 and keep the code they had with a single bf16 bit.
+template <int T, typename Epi = NoEpilogue, int C8 = 0>
 __device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& g, gptr c, int i, int j0, bool mv, unsigned int lane, const Epi& e = Epi()) {
   typename Acc<T>::type acc;
   float bias = 0.0f;
@@ -125,7 +129,7 @@ __device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& 
     biased = e.colbias != 0;
     if (biased) {                                  // one load per lane, clamped like the operand loads: rows beyond m read row m - 1 and are never stored
       const int il = min(i, g.m - 1);
-      bias = g.c_bf16 ? bf16_bits_to_f32(((GM const unsigned short*)e.d)[il]) : ((GM const float*)e.d)[il];
+      bias = g.c_kind != 0 ? bf16_bits_to_f32(((GM const unsigned short*)e.d)[il]) : ((GM const float*)e.d)[il];
     }
   }
   static_for<Acc<T>::N>([&](auto r) {
@@ -133,7 +137,10 @@ __device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& 
     float v = 0.0f;
     if (g.beta1 && mv && j < g.n) {
       const long long o = (long long)j * g.ldc + i;
-      v = g.c_bf16 ? bf16_bits_to_f32(((GM const unsigned short*)c)[o]) : ((GM const float*)c)[o];
+      if constexpr (C8 != 0) {
+        if (g.c_kind >= 2) { const unsigned char x = ((GM const unsigned char*)c)[o]; v = C8 == 2 ? hf8_to_f32(x) : bf8_to_f32(x); }
+        else v = ((GM const float*)c)[o];
+      } else v = g.c_kind != 0 ? bf16_bits_to_f32(((GM const unsigned short*)c)[o]) : ((GM const float*)c)[o];
     }
     if constexpr (Epi::fused) { if (biased) v = g.beta1 ? bias + v : bias; }
     acc[r.value] = v;
@@ -159,7 +166,7 @@ __device__ __forceinline__ void acc_relu_mask(const GemmGroupDesc& g, const Fuse
   });
 }
 
-template <int T, typename Epi = NoEpilogue>
+template <int T, typename Epi = NoEpilogue, int C8 = 0>
 __device__ __forceinline__ void acc_store(const GemmGroupDesc& g, gptr c, typename Acc<T>::type acc, int i, int j0, bool mv, unsigned int lane, const Epi& e = Epi()) {
   constexpr int N = Acc<T>::N;
   if constexpr (Epi::fused) {                      // the mask from the sums, then the activation, then the store below
@@ -167,7 +174,19 @@ __device__ __forceinline__ void acc_store(const GemmGroupDesc& g, gptr c, typena
     if (e.act == 3) static_for<N>([&](auto r) { acc[r.value] = act_fixed<3>(acc[r.value]); });
     else if (e.act != 0) static_for<N>([&](auto r) { acc[r.value] = act_fixed<1>(acc[r.value]); });
   }
-  if (g.c_bf16) {
+  if constexpr (C8 != 0) {
+    if (g.c_kind >= 2) {                           // two results per conversion (f32 -> f16 -> 8 bits, NaNs in software), one byte store each
+      static_for<N / 2>([&](auto q) {
+        constexpr int r0 = 2 * q.value, r1 = r0 + 1;
+        const unsigned int w = f32x2_to_fp8_ref(acc[r0], acc[r1], C8 == 2);
+        const int ja = j0 + acc_col<T>(r0, lane), jb = j0 + acc_col<T>(r1, lane);
+        if (mv && ja < g.n) ((GM unsigned char*)c)[(long long)ja * g.ldc + i] = (unsigned char)(w & 0xffu);
+        if (mv && jb < g.n) ((GM unsigned char*)c)[(long long)jb * g.ldc + i] = (unsigned char)(w >> 8);
+      });
+      return;
+    }
+  }
+  if (C8 == 0 && g.c_kind != 0) {
     float x[N]; unsigned int pk[N / 2];
     static_for<N>([&](auto r) { x[r] = acc[r.value]; });
     bf16_pk_exact_n<N / 2>(x, pk);
@@ -358,6 +377,93 @@ __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& c
     }
   }
   acc_store<T, Epi>(g, c, acc, i, j0, mv, lane, e);
+}
+
+// 8-bit floats (HF8: E4M3, else BF8 = E5M2): lane (i = lane % T, h = lane / T) feeds A(i, k0 + 8 h + e) and B(k0 + 8 h + e, j0 + lane % T), e < 8, per MFMA -- 8
+// consecutive k of its row / column, one 64-bit operand: a step is 16 k deep on a 32-tile (32 x 32 x 16, h < 2) and 32 k deep on a 16-tile (16 x 16 x 32, h < 4).
+// A is the VNNI-4 image, A(i, k) at byte ((k / 4) * lda + i) * 4 + k % 4, so a lane's 8 k are the two dwords (k0 / 4 + e) * lda + i, e < 2, of a 4-byte aligned
+// block (a_vec: wave-uniform, per block), else eight byte loads.  B is flat, B(k, j) at j * ldb + k: one 8-byte load of the column's k run when the block pointer
+// and ldb are multiples of 8 (b_vec8), else eight byte loads.  k is a multiple of 4 (dispatch refuses every other k).  Clamping as above: rows / columns beyond
+// m / n read row m - 1 / column n - 1 and are never stored; a wide load lies inside a whole step (k0 + 8 <= K); the ragged step reads k = K - 1 beyond K, byte by
+// byte, and replaces the value by the padding A = -0 (0x80 in both formats), B = +0.  The last byte touched is ((K / 4 - 1) * lda + m - 1) * 4 + 3 of an A block
+// and (n - 1) * ldb + K - 1 of a B block, in the wide and in the byte forms alike; the first is byte 0 of each.
+template <bool HF8> __device__ __forceinline__ f32x16 mfma_fp8(long x, long y, f32x16 acc) {
+  if constexpr (HF8) return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(x, y, acc, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf8_bf8(x, y, acc, 0, 0, 0);
+}
+template <bool HF8> __device__ __forceinline__ f32x4 mfma_fp8(long x, long y, f32x4 acc) {
+  if constexpr (HF8) return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(x, y, acc, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(x, y, acc, 0, 0, 0);
+}
+__device__ __forceinline__ unsigned char a_fp8(GM const unsigned char* ap, int lda, int i, int kx) { return ap[((long long)(kx >> 2) * lda + i) * 4 + (kx & 3)]; }
+// U consecutive MFMA steps of an 8-bit float tile from k = kk on, every operand request ahead of the first MFMA; VEC: both operands are known to take the
+// wide loads (no byte-wise code in the instance)
+template <int T, int U, bool VEC, bool HF8> __device__ __forceinline__ void steps_fp8(const GemmGroupDesc& g, typename Acc<T>::type& acc, GM const unsigned char* ap, GM const unsigned char* bp,
+  int kk, int il, int h, bool a_vec, bool b_vec) {
+  constexpr int KS = (T == 32) ? 16 : 32;
+  u32x2 x[U], y[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int k0 = kk + u * KS + 8 * h;
+    if (VEC || b_vec) x[u] = *(GM const u32x2*)(bp + k0);
+    else {
+      unsigned int w[2] = {0u, 0u};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) w[e >> 2] |= (unsigned int)bp[k0 + e] << (8 * (e & 3));
+      x[u][0] = w[0]; x[u][1] = w[1];
+    }
+    if (VEC || a_vec) {
+      GM const unsigned int* ap4 = (GM const unsigned int*)ap;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) y[u][e] = ap4[(long long)((k0 >> 2) + e) * g.lda + il];
+    } else {
+      unsigned int w[2] = {0u, 0u};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) w[e >> 2] |= (unsigned int)a_fp8(ap, g.lda, il, k0 + e) << (8 * (e & 3));
+      y[u][0] = w[0]; y[u][1] = w[1];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) acc = mfma_fp8<HF8>(__builtin_bit_cast(long, x[u]), __builtin_bit_cast(long, y[u]), acc);
+}
+template <int T, bool DEEP, bool HF8, typename Chain>
+__device__ __forceinline__ void tile_fp8(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane) {
+  constexpr int KS = (T == 32) ? 16 : 32, C8 = HF8 ? 2 : 1;
+  const int lr = (int)(lane & (T - 1)), h = (int)(lane / T);
+  const int i = i0 + lr, j = j0 + lr;
+  const bool mv = i < g.m;
+  const int il = min(i, g.m - 1);
+  typename Acc<T>::type acc = acc_start<T, NoEpilogue, C8>(g, c, i, j0, mv, lane);
+  const int K = g.k;
+  const int kbig = K - K % (4 * KS), kfull = K - K % KS;
+  gcptr an = nullptr, bn = nullptr;
+  if (ch.count) ch.fetch(0, an, bn);
+  for (unsigned long long r = 0; r < ch.count; ++r) {
+    const gcptr a = an, b = bn;
+    ch.fetch(r + 1, an, bn);
+    GM const unsigned char* ap = (GM const unsigned char*)a;
+    GM const unsigned char* bp = (GM const unsigned char*)b + (long long)min(j, g.n - 1) * g.ldb;
+    const bool a_vec = ch.a_vec4(a), b_vec = ch.b_vec8(b);
+    int kk = 0;
+    if constexpr (DEEP) {                      // segments: four steps per round of requests when both operands take the wide loads (12 more registers)
+      if (a_vec && b_vec) for (; kk < kbig; kk += 4 * KS) steps_fp8<T, 4, true, HF8>(g, acc, ap, bp, kk, il, h, true, true);
+    }
+    for (; kk < kfull; kk += KS) steps_fp8<T, 1, false, HF8>(g, acc, ap, bp, kk, il, h, a_vec, b_vec);
+    if (kk < K) {                              // ragged k (whole quads): A = -0 (0x80), B = +0 beyond K
+      const int k0 = kk + 8 * h;
+      unsigned int xw[2] = {0u, 0u}, yw[2] = {0u, 0u};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int kx = k0 + e, kc = min(kx, K - 1);
+        const unsigned int vb = bp[kc], va = a_fp8(ap, g.lda, il, kc);
+        xw[e >> 2] |= (kx < K ? vb : 0u) << (8 * (e & 3));
+        yw[e >> 2] |= (kx < K ? va : 0x80u) << (8 * (e & 3));
+      }
+      const u32x2 x = {xw[0], xw[1]}, y = {yw[0], yw[1]};
+      acc = mfma_fp8<HF8>(__builtin_bit_cast(long, x), __builtin_bit_cast(long, y), acc);
+    }
+  }
+  acc_store<T, NoEpilogue, C8>(g, c, acc, i, j0, mv, lane);
 }
 
 // f64, one 16 x 16 tile: lane (g = lane % 16, s = lane / 16) feeds A(i0 + g, k0 + s) and B(k0 + s, j0 + g) per MFMA and holds C(i0 + g, j0 + s + 4 r) in

@@ -31,6 +31,9 @@
 // of a workspace as destinations, pass 2 adds a block's partials in ascending slice order.  The entries above never split a segment.
 // The two ext *_sliced entries are the same two passes with the FusedEpilogue's operators applied to the blocks' sums in pass 2
 // (gemm_segments_slice_reduce_fused_kernel); pass 1 is launched exactly as for the plain handles.
+// 8-bit floats (classes 3 BF8 and 4 HF8): BF8 x BF8 -> f32 / BF8 and HF8 x HF8 -> f32 / HF8 through tile_fp8 (gemm_group_tile.hpp) in the
+// plain ADDRESS, OFFSET and sliced kernels -- A VNNI-4, NN only, so the offsets kernels have the <0,0> instance alone; never fused.  Pass 2 stores an 8-bit C
+// through the instances <3> / <4> of gemm_segments_slice_reduce_kernel.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "internal.hpp"
@@ -85,10 +88,16 @@ struct OffsetSegEpilogue {
   }
 };
 
-// CLS: 0 f32, 1 bf16, 2 f64 (16 x 16 tiles only, no epilogue).  The tile edge is a wave-uniform runtime value, the class and the transposes pick the instance.
+// CLS: 0 f32, 1 bf16, 2 f64 (16 x 16 tiles only, no epilogue), 3 BF8, 4 HF8 (NN only, no epilogue; C f32 or the operands' type).  The tile edge is a
+// wave-uniform runtime value, the class and the transposes pick the instance.
 template <int CLS, bool TA, bool TB, typename Chain, typename Epi>
 __device__ __forceinline__ void segment_tile(const GemmGroupDesc& g, const Chain& ch, gptr c, int tm, int tn, unsigned int lane, const Epi& e) {
   if constexpr (CLS == 2) tile_f64<Chain, TA, TB>(g, ch, c, tm * 16, tn * 16, lane);
+  else if constexpr (CLS >= 3) {
+    static_assert(!TA && !TB && !Epi::fused, "8-bit float segments: NN, without operators");
+    if (g.tile == 32) tile_fp8<32, true, CLS == 4, Chain>(g, ch, c, tm * 32, tn * 32, lane);
+    else tile_fp8<16, true, CLS == 4, Chain>(g, ch, c, tm * 16, tn * 16, lane);
+  }
   else if (g.tile == 32) {
     if constexpr (CLS == 1) tile_bf16<32, true, Chain, Epi, TA, TB>(g, ch, c, tm * 32, tn * 32, lane, e);
     else tile_f32<32, true, Chain, Epi, TA, TB>(g, ch, c, tm * 32, tn * 32, lane, e);
@@ -98,7 +107,7 @@ __device__ __forceinline__ void segment_tile(const GemmGroupDesc& g, const Chain
   }
 }
 
-// The item loop of all 25 kernels.  Per item, in this order: seg_ptr[s], seg_ptr[s + 1], C's address, the epilogue's entries, then the chain.
+// The item loop of every kernel but the two pass-2 families.  Per item, in this order: seg_ptr[s], seg_ptr[s + 1], C's address, the epilogue's entries, then the chain.
 template <int CLS, bool TA, bool TB, typename Source, typename SegEpilogue>
 __device__ __forceinline__ void segments_items(const GemmGroupDesc& g, const unsigned long long* seg_ptr, Source src, SegEpilogue sep, unsigned long long total) {
   const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -124,6 +133,8 @@ __device__ __forceinline__ void segments_items(const GemmGroupDesc& g, const uns
 XAMD_SEG_KERNEL(gemm_segments_f32_kernel, 0)
 XAMD_SEG_KERNEL(gemm_segments_bf16_kernel, 1)
 XAMD_SEG_KERNEL(gemm_segments_f64_kernel, 2)
+XAMD_SEG_KERNEL(gemm_segments_bf8_kernel, 3)
+XAMD_SEG_KERNEL(gemm_segments_hf8_kernel, 4)
 #undef XAMD_SEG_KERNEL
 
 #define XAMD_SEG_FUSED_KERNEL(NAME, CLS) \
@@ -141,6 +152,8 @@ XAMD_SEG_FUSED_KERNEL(gemm_segments_bf16_fused_kernel, 1)
 XAMD_OFFS_KERNEL(gemm_segments_offs_f32_kernel, 0)
 XAMD_OFFS_KERNEL(gemm_segments_offs_bf16_kernel, 1)
 XAMD_OFFS_KERNEL(gemm_segments_offs_f64_kernel, 2)
+XAMD_OFFS_KERNEL(gemm_segments_offs_bf8_kernel, 3)          // 8-bit floats: only the NN instance <0,0> exists
+XAMD_OFFS_KERNEL(gemm_segments_offs_hf8_kernel, 4)
 #undef XAMD_OFFS_KERNEL
 
 #define XAMD_OFFS_FUSED_KERNEL(NAME, CLS) \
@@ -169,6 +182,8 @@ template <typename Base> struct SlicedSource {
 XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_f32_kernel, 0)
 XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_bf16_kernel, 1)
 XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_f64_kernel, 2)
+XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_bf8_kernel, 3)
+XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_hf8_kernel, 4)
 #undef XAMD_SEG_SLICED_KERNEL
 
 #define XAMD_OFFS_SLICED_KERNEL(NAME, CLS) \
@@ -178,21 +193,31 @@ XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_f64_kernel, 2)
 XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_f32_kernel, 0)
 XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_bf16_kernel, 1)
 XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_f64_kernel, 2)
+XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_bf8_kernel, 3)   // <0,0> only
+XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_hf8_kernel, 4)
 #undef XAMD_OFFS_SLICED_KERNEL
 
 // Pass 2: acc = C (beta = 1) or +0, then acc += P_j for the block's slices j in ASCENDING order -- one IEEE add each in the accumulator type (the kernels run
 // with denormals kept), no atomics, no arrival order -- then one store with C's ldc and type.  CLS: 0 f32 partials -> f32 C, 1 f32 partials -> bf16 C
-// (bf16_cvt.hpp: one rounding), 2 f64.  Bandwidth-bound: a work item is (block, run of 64 x V elements of the dense partial), V = 16 bytes of accumulators, so
+// (bf16_cvt.hpp: one rounding), 2 f64, 3 / 4 f32 partials -> BF8 / HF8 C (widened on the way in; out through f32x2_to_fp8_ref, the two-step rounding the
+// unsliced kernels store with: a lane's four bytes are one dword store under `wide`).  Bandwidth-bound: a work item is (block, run of 64 x V elements of the dense partial), V = 16 bytes of accumulators, so
 // lane l owns the elements (64 run + l) V .. + V - 1 of EVERY slice of the block and a wave's load of one slice is 1 KiB contiguous.  Four slices' loads are in
 // flight before the first add; a block's last one to three slices go one by one.  A lane's last load may reach past m * n into the partial's padding (inside
 // the workspace by construction of g.sc; never added into anything stored).  blk_ptr[b], blk_ptr[b + 1] and C's entry are wave-uniform scalar loads like the
 // item heads of pass 1, and the waves grid-stride in the same way.  C is read only under beta = 1 and written for i < m, j < n only: with m a multiple of V and
 // columns and block V-element aligned (`wide_ld`, then the pointer) a lane's V elements are one load / store of C, else element by element.  A block without
 // slices: beta = 0 stores +0, beta = 1 is skipped.  No LDS, no scratch, vector stores only.
+// an element of C as the accumulator it starts
+template <int CLS, typename X> __device__ __forceinline__ auto slice_c_widen(X x) {
+  if constexpr (CLS == 1) return bf16_bits_to_f32(x);
+  else if constexpr (CLS == 3) return bf8_to_f32(x);
+  else if constexpr (CLS == 4) return hf8_to_f32(x);
+  else return x;
+}
 template <int CLS>
 __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSliceReduce q, unsigned long long total) {
   typedef typename std::conditional<CLS == 2, double, float>::type acc_t;
-  typedef typename std::conditional<CLS == 2, double, typename std::conditional<CLS == 1, unsigned short, float>::type>::type c_t;
+  typedef typename std::conditional<CLS == 2, double, typename std::conditional<CLS == 1, unsigned short, typename std::conditional<CLS >= 3, unsigned char, float>::type>::type>::type c_t;
   constexpr int V = 16 / (int)sizeof(acc_t);
   typedef acc_t vec_t __attribute__((ext_vector_type(V)));
   typedef c_t cvec_t __attribute__((ext_vector_type(V)));
@@ -219,15 +244,12 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSli
       if (wide) {
         const cvec_t x = *(GM const cvec_t*)cw;
 #pragma unroll
-        for (int v = 0; v < V; ++v) { if constexpr (CLS == 1) acc[v] = bf16_bits_to_f32(x[v]); else acc[v] = x[v]; }
+        for (int v = 0; v < V; ++v) acc[v] = slice_c_widen<CLS>(x[v]);
       } else {
         unsigned int i = i0, j = j0;
 #pragma unroll
         for (int v = 0; v < V; ++v) {
-          if (live && e0 + v < mn) {
-            const c_t x = ((GM const c_t*)c)[(long long)j * q.ldc + i];
-            if constexpr (CLS == 1) acc[v] = bf16_bits_to_f32(x); else acc[v] = x;
-          }
+          if (live && e0 + v < mn) acc[v] = slice_c_widen<CLS>(((GM const c_t*)c)[(long long)j * q.ldc + i]);
           if (++i == (unsigned int)q.m) { i = 0; ++j; }
         }
       }
@@ -241,7 +263,18 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSli
     }
     for (; s < s1; ++s) { acc += *(GM const vec_t*)p; p += q.pstride; }
     if (!live) continue;
-    if constexpr (CLS == 1) {
+    if constexpr (CLS >= 3) {
+      const unsigned int w = f32x2_to_fp8_ref((float)acc[0], (float)acc[1], CLS == 4) | (f32x2_to_fp8_ref((float)acc[2], (float)acc[3], CLS == 4) << 16);
+      if (wide) *(GM unsigned int*)cw = w;
+      else {
+        unsigned int i = i0, j = j0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          if (e0 + v < mn) ((GM unsigned char*)c)[(long long)j * q.ldc + i] = (unsigned char)((w >> (8 * v)) & 0xffu);
+          if (++i == (unsigned int)q.m) { i = 0; ++j; }
+        }
+      }
+    } else if constexpr (CLS == 1) {
       float x[V]; unsigned int pk[V / 2];
 #pragma unroll
       for (int v = 0; v < V; ++v) x[v] = acc[v];
@@ -468,13 +501,16 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_fused_kernel(G
 
 // the four instances of an offsets kernel, indexed by forms & 3 (bit 0 TRANS_A, bit 1 TRANS_B)
 #define XAMD_FORMS(NAME) {NAME "<0,0>", NAME "<1,0>", NAME "<0,1>", NAME "<1,1>"}
-static const char* const kSlicedNames[3] = {"gemm_segments_sliced_f32_kernel", "gemm_segments_sliced_bf16_kernel", "gemm_segments_sliced_f64_kernel"};
-static const char* const kOffsSlicedNames[3][4] = {XAMD_FORMS("gemm_segments_offs_sliced_f32_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf16_kernel"),
-  XAMD_FORMS("gemm_segments_offs_sliced_f64_kernel")};
-static const char* const kListNames[5] = {"gemm_segments_f32_kernel", "gemm_segments_bf16_kernel", "gemm_segments_f64_kernel", "gemm_segments_f32_fused_kernel",
-  "gemm_segments_bf16_fused_kernel"};
-static const char* const kOffsNames[5][4] = {XAMD_FORMS("gemm_segments_offs_f32_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_kernel"), XAMD_FORMS("gemm_segments_offs_f64_kernel"),
-  XAMD_FORMS("gemm_segments_offs_f32_fused_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_fused_kernel")};
+// rows: the classes 0 .. 4 (f32, bf16, f64, BF8, HF8), then (unsliced) the two fused classes; the 8-bit float offsets kernels have the NN instance only
+static const char* const kSlicedNames[5] = {"gemm_segments_sliced_f32_kernel", "gemm_segments_sliced_bf16_kernel", "gemm_segments_sliced_f64_kernel",
+  "gemm_segments_sliced_bf8_kernel", "gemm_segments_sliced_hf8_kernel"};
+static const char* const kOffsSlicedNames[5][4] = {XAMD_FORMS("gemm_segments_offs_sliced_f32_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf16_kernel"),
+  XAMD_FORMS("gemm_segments_offs_sliced_f64_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf8_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_hf8_kernel")};
+static const char* const kListNames[7] = {"gemm_segments_f32_kernel", "gemm_segments_bf16_kernel", "gemm_segments_f64_kernel", "gemm_segments_bf8_kernel",
+  "gemm_segments_hf8_kernel", "gemm_segments_f32_fused_kernel", "gemm_segments_bf16_fused_kernel"};
+static const char* const kOffsNames[7][4] = {XAMD_FORMS("gemm_segments_offs_f32_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_kernel"), XAMD_FORMS("gemm_segments_offs_f64_kernel"),
+  XAMD_FORMS("gemm_segments_offs_bf8_kernel"), XAMD_FORMS("gemm_segments_offs_hf8_kernel"), XAMD_FORMS("gemm_segments_offs_f32_fused_kernel"),
+  XAMD_FORMS("gemm_segments_offs_bf16_fused_kernel")};
 #undef XAMD_FORMS
 
 template <bool TA, bool TB>
@@ -487,6 +523,10 @@ static void launch_offs_form(const SegmentsLaunch& l, unsigned int grid, hipStre
     return;
   }
   const int a_wide = (l.forms >> 2) & 3;
+  if constexpr (!TA && !TB) {                              // 8-bit floats: the host refuses the transposed forms
+    if (l.cls == 3) { hipLaunchKernelGGL((gemm_segments_offs_bf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items); return; }
+    if (l.cls == 4) { hipLaunchKernelGGL((gemm_segments_offs_hf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items); return; }
+  }
   if (l.cls == 2) hipLaunchKernelGGL((gemm_segments_offs_f64_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
   else if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_bf16_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
   else hipLaunchKernelGGL((gemm_segments_offs_f32_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
@@ -498,7 +538,9 @@ static void launch_list(const SegmentsLaunch& l, unsigned int grid, hipStream_t 
     const GemmSegEpilogue& e = *(const GemmSegEpilogue*)l.epilogue;
     if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
     else hipLaunchKernelGGL(gemm_segments_f32_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
-  } else if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_f64_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+  } else if (l.cls == 4) hipLaunchKernelGGL(gemm_segments_hf8_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+  else if (l.cls == 3) hipLaunchKernelGGL(gemm_segments_bf8_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+  else if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_f64_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
   else if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
   else hipLaunchKernelGGL(gemm_segments_f32_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
 }
@@ -507,6 +549,10 @@ template <bool TA, bool TB>
 static void launch_offs_sliced_form(const SegmentsLaunch& l, const GemmGroupDesc& g, unsigned int grid, hipStream_t st) {
   const long long* a_offs = (const long long*)l.a_list; const long long* b_offs = (const long long*)l.b_list;
   const int a_wide = (l.forms >> 2) & 3;
+  if constexpr (!TA && !TB) {
+    if (l.cls == 3) { hipLaunchKernelGGL((gemm_segments_offs_sliced_bf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items); return; }
+    if (l.cls == 4) { hipLaunchKernelGGL((gemm_segments_offs_sliced_hf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items); return; }
+  }
   if (l.cls == 2) hipLaunchKernelGGL((gemm_segments_offs_sliced_f64_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
   else if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_sliced_bf16_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
   else hipLaunchKernelGGL((gemm_segments_offs_sliced_f32_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
@@ -518,11 +564,13 @@ static int launch_sliced(const SegmentsLaunch& l, hipStream_t st, const char** k
   const int V = l.cls == 2 ? 2 : 4;                        // accumulators in 16 bytes
   if (l.items != 0) {
     GemmGroupDesc g = l.g;                                 // pass 1 writes partials: beta = 0, accumulator-typed, dense, `pstride` bytes apart in the workspace
-    g.beta1 = 0; g.c_bf16 = 0; g.ldc = g.m; g.c = (char*)l.workspace; g.sc = l.pstride;
+    g.beta1 = 0; g.c_kind = 0; g.ldc = g.m; g.c = (char*)l.workspace; g.sc = l.pstride;
     const unsigned int grid = group_grid(l.items);
     if (!l.offsets) {
       const void* const* a_list = (const void* const*)l.a_list; const void* const* b_list = (const void* const*)l.b_list;
-      if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_sliced_f64_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+      if (l.cls == 4) hipLaunchKernelGGL(gemm_segments_sliced_hf8_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+      else if (l.cls == 3) hipLaunchKernelGGL(gemm_segments_sliced_bf8_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+      else if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_sliced_f64_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
       else if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_sliced_bf16_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
       else hipLaunchKernelGGL(gemm_segments_sliced_f32_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
     } else switch (l.forms & 3) {
@@ -551,19 +599,21 @@ static int launch_sliced(const SegmentsLaunch& l, hipStream_t st, const char** k
       const GemmSegEpilogue& o = *(const GemmSegEpilogue*)l.epilogue;
       e.d_list = o.d_list; e.d = o.d; e.mask_list = o.mask_list; e.colbias = o.colbias; e.act = o.act; e.mask_ld = o.mask_ld;
     }
-    if (l.g.c_bf16) hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<1>, dim3(grid), dim3(256), 0, st, q, e, total);
+    if (l.g.c_kind == 1) hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<1>, dim3(grid), dim3(256), 0, st, q, e, total);
     else hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<0>, dim3(grid), dim3(256), 0, st, q, e, total);
     return (int)hipGetLastError();
   }
   if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<2>, dim3(grid), dim3(256), 0, st, q, total);
-  else if (l.g.c_bf16) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<1>, dim3(grid), dim3(256), 0, st, q, total);
+  else if (l.g.c_kind == 1) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<1>, dim3(grid), dim3(256), 0, st, q, total);
+  else if (l.g.c_kind == 2) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<3>, dim3(grid), dim3(256), 0, st, q, total);
+  else if (l.g.c_kind == 3) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<4>, dim3(grid), dim3(256), 0, st, q, total);
   else hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<0>, dim3(grid), dim3(256), 0, st, q, total);
   return (int)hipGetLastError();
 }
 
 int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname) {
   if (l.sliced) return launch_sliced(l, (hipStream_t)stream, kname);
-  const int row = l.fused ? (l.cls == 1 ? 4 : 3) : l.cls;
+  const int row = l.fused ? (l.cls == 1 ? 6 : 5) : l.cls;
   *kname = l.offsets ? kOffsNames[row][l.forms & 3] : kListNames[row];
   if (l.items == 0) return 0;
   const unsigned int grid = group_grid(l.items);

@@ -2275,8 +2275,11 @@ static GroupShape group_shape(const libxsmm_gemm_descriptor& d, unsigned int f, 
   const bool f32 = d.a_type == LIBXSMM_DATATYPE_F32 && d.b_type == LIBXSMM_DATATYPE_F32 && d.c_type == LIBXSMM_DATATYPE_F32;
   const bool f64 = d.a_type == LIBXSMM_DATATYPE_F64 && d.b_type == LIBXSMM_DATATYPE_F64 && d.c_type == LIBXSMM_DATATYPE_F64;
   const bool bf16 = d.a_type == LIBXSMM_DATATYPE_BF16 && d.b_type == LIBXSMM_DATATYPE_BF16 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF16);
-  if (!f32 && !f64 && !bf16) return kGroupShapeTypes;
-  cls = f64 ? 2 : (bf16 ? 1 : 0);
+  // the 8-bit floats (segments only: grouped_eligible sends classes 3 and 4 on their own way): BF8 x BF8 -> f32 / BF8, HF8 x HF8 -> f32 / HF8
+  const bool bf8 = d.a_type == LIBXSMM_DATATYPE_BF8 && d.b_type == LIBXSMM_DATATYPE_BF8 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF8);
+  const bool hf8 = d.a_type == LIBXSMM_DATATYPE_HF8 && d.b_type == LIBXSMM_DATATYPE_HF8 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_HF8);
+  if (!f32 && !f64 && !bf16 && !bf8 && !hf8) return kGroupShapeTypes;
+  cls = f64 ? 2 : (bf16 ? 1 : (bf8 ? 3 : (hf8 ? 4 : 0)));
   if (f & ~(kGroupTileFlags | own)) return kGroupShapeFlags;
   // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers); a transposed operand spans lda x m / ldb x k
   const bool ta = (f & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (f & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
@@ -2287,8 +2290,8 @@ static GroupShape group_shape(const libxsmm_gemm_descriptor& d, unsigned int f, 
   g.m = (int)d.m; g.n = (int)d.n; g.k = (int)d.k; g.lda = (int)d.lda; g.ldb = (int)d.ldb; g.ldc = (int)d.ldc;
   g.tile = tile; g.tiles_m = (int)((d.m + tile - 1) / tile); g.tiles_n = (int)((d.n + tile - 1) / tile);
   g.beta1 = (f & LIBXSMM_GEMM_FLAG_BETA_0) ? 0 : 1;
-  g.vnni_a = (bf16 && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
-  g.c_bf16 = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : 0;
+  g.vnni_a = ((bf16 || bf8 || hf8) && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
+  g.c_kind = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : (d.c_type == LIBXSMM_DATATYPE_BF8 ? 2 : (d.c_type == LIBXSMM_DATATYPE_HF8 ? 3 : 0));
   return kGroupShapeOk;
 }
 // ---- grouped batches (libxsmm_hip_gemm_batch_grouped, libxsmm_hip_gemm_ext_batch_grouped) and group plans (libxsmm_hip_gemm_group_plan_*) ------------------
@@ -2322,7 +2325,7 @@ template <typename Group> static bool grouped_eligible(const KernelCtx* k, const
   if (k->kind != K_GEMM) return false;
   const libxsmm_gemm_descriptor& d = k->g;
   const unsigned int f = effective_gemm_flags(d);
-  if (group_shape(d, f, LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE | (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI), g, cls) != kGroupShapeOk || cls == 2) return false;
+  if (group_shape(d, f, LIBXSMM_GEMM_FLAG_BATCH_REDUCE_STRIDE | (d.flags & LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI), g, cls) != kGroupShapeOk || cls >= 2) return false;
   const libxsmm_gemm_param& p = *(const libxsmm_gemm_param*)&grp.param;
   if (d.m == 0 || d.n == 0 || d.k == 0 || !p.a.primary || !p.b.primary || !p.c.primary) return false;
   unsigned long long brc = 1;
@@ -2576,7 +2579,7 @@ LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan
 // What the four segments entries ask of their arguments and their handle, in one place: every refusal is set here, before anything is launched.  `ext` is the
 // entry (the two libxsmm_hip_gemm_ext_batch_reduce_segments* entries take ext handles and only those); `forms` != NULL is one of the two *_offsets entries, which
 // take OFFSET handles, three bases in param's primary slots (the lists are then a_offs / b_offs / c_offs) and transposed operands: *forms receives the bits
-// their kernels read.  (a, b and c sit at the same place in libxsmm_gemm_param and libxsmm_gemm_ext_param.)  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64) and `tiles` the C tiles of one segment.
+// their kernels read.  (a, b and c sit at the same place in libxsmm_gemm_param and libxsmm_gemm_ext_param.)  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64, 3 BF8, 4 HF8) and `tiles` the C tiles of one segment.
 struct SegmentsSliced;
 static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, GemmGroupDesc& g, int& cls, unsigned long long& tiles,
   int* forms, const SegmentsSliced* sl);
@@ -2631,10 +2634,14 @@ static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, 
     (ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
   const GroupShape shape = group_shape(d, f, own, g, cls);
   if (shape == kGroupShapeTypes) {
-    set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return nullptr;
+    set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16, bf8 -> f32 / bf8, hf8 -> f32 / hf8)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return nullptr;
   }
   const bool ta = (f & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (f & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
   if (!offsets && (ta || tb)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return nullptr; }
+  if (cls >= 3 && shape != kGroupShapeTypes) {               // the 8-bit floats: the matrix-core layout of the dense kernels, NN
+    if (ta || tb) { set_error(-3, "%s: transposed 8-bit float operands are not taken (BF8 / HF8 handles: NN only)", fn); return nullptr; }
+    if (!(f & LIBXSMM_GEMM_FLAG_VNNI_A)) { set_error(-3, "%s: an 8-bit float A is taken as VNNI-4 only (LIBXSMM_GEMM_FLAG_VNNI_A)", fn); return nullptr; }
+  }
   if (f & (LIBXSMM_GEMM_FLAG_VNNI_B | LIBXSMM_GEMM_FLAG_VNNI_C)) { set_error(-3, "%s: VNNI layouts of B and C are not taken (A flat or VNNI-2, B and C flat)", fn); return nullptr; }
   if (ta && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) { set_error(-3, "%s: a VNNI-2 A is not taken together with TRANS_A (a transposed A is flat)", fn); return nullptr; }
   if (shape == kGroupShapeFlags) {
@@ -2643,8 +2650,8 @@ static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, 
   }
   if (shape == kGroupShapeLd) { set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return nullptr; }
   // what the leading dimension allows of the wider loads; the block pointers are tested per product on the device
-  const unsigned long long esz = cls == 1 ? 2 : (cls == 2 ? 8 : 4), colb = (unsigned long long)d.ldb * esz;
-  g.a_vec4 = cls == 1 ? 1 : 0; g.b_vec16 = (!tb && (colb & 15) == 0) ? 1 : 0; g.b_vec8 = (!tb && (colb & 7) == 0) ? 1 : 0;
+  const unsigned long long esz = cls == 1 ? 2 : (cls == 2 ? 8 : (cls >= 3 ? 1 : 4)), colb = (unsigned long long)d.ldb * esz;
+  g.a_vec4 = (cls == 1 || cls >= 3) ? 1 : 0; g.b_vec16 = (!tb && (colb & 15) == 0) ? 1 : 0; g.b_vec8 = (!tb && (colb & 7) == 0) ? 1 : 0;
   if (offsets) {
     const libxsmm_gemm_param* q = (const libxsmm_gemm_param*)param;
     if (q) { g.a = (const char*)q->a.primary; g.b = (const char*)q->b.primary; g.c = (char*)q->c.primary; }
@@ -2661,13 +2668,14 @@ static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, 
   return k;
 }
 // The operators of an ext handle as the fused segment kernels take them, decoded as run_gemm decodes them: colbias, and act 0 none, 1 ReLU, 2 ReLU + bitmask,
-// 3 sigmoid.  false (the error is set) for every other operator and for f64 with any.
+// 3 sigmoid.  false (the error is set) for every other operator and for f64 and the 8-bit floats with any.
 static bool segments_operators(const char* fn, const libxsmm_gemm_descriptor& d, int cls, int& colbias_out, int& act) {
   if (!fused_operators(d, colbias_out, act)) {
     set_error(-3, "%s: fused operator not taken (column-broadcast BINARY_ADD, cp RELU with or without bitmask, cp SIGMOID only)", fn); return false;
   }
   const bool colbias = colbias_out != 0;
   if (cls == 2 && (colbias || act != 0)) { set_error(-3, "%s: f64 ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
+  if (cls >= 3 && (colbias || act != 0)) { set_error(-3, "%s: 8-bit float ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
   return true;
 }
 // The one path behind the four entries.  `offsets`: the lists hold signed byte offsets from the bases in param [ref: gemm ref :509-513, :186-188] -- a
