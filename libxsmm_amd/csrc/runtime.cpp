@@ -1074,6 +1074,74 @@ void run_pgemm(KernelCtx* k, const void* param) {
   finish_launch(err, kname);
 }
 
+// where a pointer lives as the runtime sees it; hipMemoryTypeUnregistered for one it does not know (plain host memory: the sticky error of the query is cleared)
+static hipMemoryType pointer_type(const void* q) {
+  hipPointerAttribute_t attr;
+  const hipError_t e = hipPointerGetAttributes(&attr, q);
+  (void)hipGetLastError();
+  return e == hipSuccess ? attr.type : hipMemoryTypeUnregistered;
+}
+
+// A BCSC pattern that arrived in HOST memory (the reference's calling convention: plain malloc'd colptr / rowidx [ref: spmm_kernel.c:306-347]).
+// It is readable here, so it is inverted on the host -- table[n-block][k-block] = block id -- and kept on the device with its key:
+// a pattern rarely changes between calls, and a call with a known pattern then costs no staging copy and no inversion kernel.
+// Returns the cached entry (d_block = [colptr | rowidx (at least one word) | table]), or null with the error set.
+static const KernelCtx::BcscCached* bcsc_host_pattern(KernelCtx* k, const unsigned int* hc, const unsigned int* hr, unsigned long long nblk_n, int nkb, int bn) {
+  const unsigned int nnzb = hc[nblk_n];
+  const size_t n_ptr = (size_t)nblk_n + 1, n_idx = std::max<size_t>(1, nnzb), n_tab = std::max<size_t>(1, (size_t)nblk_n * nkb);
+  // key = [nblk_n, nkb, colptr..., rowidx...]; compared in place against the caller's arrays: the hit path neither allocates nor locks
+  const auto matches = [&](const KernelCtx::BcscCached* e) {
+    return e && e->pattern.size() == 2 + n_ptr + nnzb && e->pattern[0] == (unsigned int)nblk_n && e->pattern[1] == (unsigned int)nkb &&
+           std::memcmp(e->pattern.data() + 2, hc, n_ptr * sizeof(unsigned int)) == 0 &&
+           (nnzb == 0 || std::memcmp(e->pattern.data() + 2 + n_ptr, hr, (size_t)nnzb * sizeof(unsigned int)) == 0);
+  };
+  const KernelCtx::BcscCached* hit = k->bcsc_last.load(std::memory_order_acquire);
+  if (matches(hit)) return hit;
+  static std::mutex cache_lock;
+  std::lock_guard<std::mutex> guard(cache_lock);
+  hit = nullptr;
+  for (const auto* e : k->bcsc_cache) if (matches(e)) { hit = e; break; }
+  if (!hit) {
+    std::vector<unsigned int> img(n_ptr + n_idx + n_tab, 0xffffffffu);
+    std::copy(hc, hc + n_ptr, img.begin()); std::copy(hr, hr + nnzb, img.begin() + n_ptr);
+    for (unsigned long long nb = 0; nb < nblk_n; ++nb) {
+      if (hc[nb] > hc[nb + 1] || hc[nb + 1] > nnzb) { set_error(-2, "BCSC colptr is not monotone"); return nullptr; }
+      for (unsigned int b = hc[nb]; b < hc[nb + 1]; ++b) {
+        if (hr[b] >= (unsigned int)nkb) { set_error(-2, "BCSC rowidx[%u] = %u is outside the %d k-blocks", b, hr[b], nkb); return nullptr; }
+        img[n_ptr + n_idx + nb * nkb + hr[b]] = b;
+      }
+    }
+    unsigned int* blockp = nullptr;
+    if (!hip_ok(hipMalloc((void**)&blockp, img.size() * sizeof(unsigned int)), "hipMalloc(BCSC pattern)")) return nullptr;
+    if (!hip_ok(hipMemcpy(blockp, img.data(), img.size() * sizeof(unsigned int), hipMemcpyHostToDevice), "hipMemcpy(BCSC pattern)")) return nullptr;
+    KernelCtx::BcscCached* fresh = new KernelCtx::BcscCached();
+    fresh->pattern.reserve(2 + n_ptr + nnzb);
+    fresh->pattern.push_back((unsigned int)nblk_n); fresh->pattern.push_back((unsigned int)nkb);
+    fresh->pattern.insert(fresh->pattern.end(), hc, hc + n_ptr); fresh->pattern.insert(fresh->pattern.end(), hr, hr + nnzb);
+    fresh->d_block = blockp;
+    if (nkb <= 64 && bn > 0)        // the k-blocks the first 64 columns use (see BcscArgs::kmask0)
+      for (unsigned long long nb = 0; nb < nblk_n && nb * (unsigned long long)bn < 64ull; ++nb)
+        for (unsigned int b = hc[nb]; b < hc[nb + 1]; ++b) fresh->kmask0 |= 1ull << hr[b];
+    // an evicted entry stays alive until the kernel is released: another thread may be past its lock-free hit, a launch may still read its table
+    if (k->bcsc_cache.size() >= 4) { k->bcsc_old.push_back(k->bcsc_cache.front()); k->bcsc_cache.erase(k->bcsc_cache.begin()); }
+    // ... but a caller that cycles through many patterns must not grow device memory without bound (advisor, round 3): beyond 64 retired entries that still own a device table the
+    // tables of the oldest 32 are freed after the device has drained (no launch can still read them; a thread would have to sit between its lock-free hit and
+    // its launch across 32 pattern insertions for the pointer to matter).  The small host parts stay until the kernel is released.
+    size_t live_old = 0;
+    for (auto* e : k->bcsc_old) live_old += e->d_block ? 1 : 0;
+    if (live_old > 64) {
+      (void)hipDeviceSynchronize();
+      size_t freed = 0;
+      for (auto* e : k->bcsc_old) { if (freed == 32) break; if (e->d_block) { (void)hipFree(e->d_block); e->d_block = nullptr; ++freed; } }
+    }
+    k->bcsc_cache.push_back(fresh);
+    k->device = cur_device();
+    hit = fresh;
+  }
+  k->bcsc_last.store(hit, std::memory_order_release);
+  return hit;
+}
+
 void run_bcsc(KernelCtx* k, const void* param) {
   const libxsmm_gemm_param* p = (const libxsmm_gemm_param*)param;
   const libxsmm_gemm_descriptor& d = k->g;
@@ -1088,96 +1156,33 @@ void run_bcsc(KernelCtx* k, const void* param) {
   if (!p->b.secondary || !p->b.tertiary) { set_error(-2, "BCSC kernel needs colptr in b.secondary and rowidx in b.tertiary"); return; }
   if (k->device != cur_device() && !k->bcsc_cache.empty()) { set_error(-3, "BCSC kernel holds a cached pattern on device %d but is called on device %d", k->device, cur_device()); return; }
   const int nkb = (a.bk > 0 && a.K % a.bk == 0) ? a.K / a.bk : 0;
-  hipPointerAttribute_t attr;
-  const auto on_host = [&](const void* q) {
-    const hipError_t e = hipPointerGetAttributes(&attr, q);
-    const bool host = (e != hipSuccess) || attr.type == hipMemoryTypeUnregistered || attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return host;
-  };
+  const auto on_host = [](const void* q) { const hipMemoryType t = pointer_type(q); return t == hipMemoryTypeUnregistered || t == hipMemoryTypeHost; };
   if (nkb > 0 && on_host(p->b.secondary) && on_host(p->b.tertiary)) {
-    // The pattern arrived in HOST memory (the reference's calling convention: plain malloc'd colptr / rowidx [ref: spmm_kernel.c:306-347]).
-    // It is readable here, so it is inverted on the host -- table[n-block][k-block] = block id -- and kept on the device with its key:
-    // a pattern rarely changes between calls, and a call with a known pattern then costs no staging copy and no inversion kernel.
-    const unsigned int* hc = (const unsigned int*)p->b.secondary; const unsigned int* hr = (const unsigned int*)p->b.tertiary;
+    const unsigned int* hc = (const unsigned int*)p->b.secondary;
+    const KernelCtx::BcscCached* hit = bcsc_host_pattern(k, hc, (const unsigned int*)p->b.tertiary, nblk_n, nkb, a.bn);
+    if (!hit) return;
     const unsigned int nnzb = hc[nblk_n];
-    const size_t n_ptr = (size_t)nblk_n + 1, n_idx = std::max<size_t>(1, nnzb), n_tab = std::max<size_t>(1, (size_t)nblk_n * nkb);
-    // key = [nblk_n, nkb, colptr..., rowidx...]; compared in place against the caller's arrays: the hit path neither allocates nor locks
-    const auto matches = [&](const KernelCtx::BcscCached* e) {
-      return e && e->pattern.size() == 2 + n_ptr + nnzb && e->pattern[0] == (unsigned int)nblk_n && e->pattern[1] == (unsigned int)nkb &&
-             std::memcmp(e->pattern.data() + 2, hc, n_ptr * sizeof(unsigned int)) == 0 &&
-             (nnzb == 0 || std::memcmp(e->pattern.data() + 2 + n_ptr, hr, (size_t)nnzb * sizeof(unsigned int)) == 0);
-    };
-    const KernelCtx::BcscCached* hit = k->bcsc_last.load(std::memory_order_acquire);
-    if (!matches(hit)) {
-      static std::mutex cache_lock;
-      std::lock_guard<std::mutex> guard(cache_lock);
-      hit = nullptr;
-      for (const auto* e : k->bcsc_cache) if (matches(e)) { hit = e; break; }
-      if (!hit) {
-        std::vector<unsigned int> img(n_ptr + n_idx + n_tab, 0xffffffffu);
-        std::copy(hc, hc + n_ptr, img.begin()); std::copy(hr, hr + nnzb, img.begin() + n_ptr);
-        for (unsigned long long nb = 0; nb < nblk_n; ++nb) {
-          if (hc[nb] > hc[nb + 1] || hc[nb + 1] > nnzb) { set_error(-2, "BCSC colptr is not monotone"); return; }
-          for (unsigned int b = hc[nb]; b < hc[nb + 1]; ++b) {
-            if (hr[b] >= (unsigned int)nkb) { set_error(-2, "BCSC rowidx[%u] = %u is outside the %d k-blocks", b, hr[b], nkb); return; }
-            img[n_ptr + n_idx + nb * nkb + hr[b]] = b;
-          }
-        }
-        unsigned int* blockp = nullptr;
-        if (!hip_ok(hipMalloc((void**)&blockp, img.size() * sizeof(unsigned int)), "hipMalloc(BCSC pattern)")) return;
-        if (!hip_ok(hipMemcpy(blockp, img.data(), img.size() * sizeof(unsigned int), hipMemcpyHostToDevice), "hipMemcpy(BCSC pattern)")) return;
-        KernelCtx::BcscCached* fresh = new KernelCtx::BcscCached();
-        fresh->pattern.reserve(2 + n_ptr + nnzb);
-        fresh->pattern.push_back((unsigned int)nblk_n); fresh->pattern.push_back((unsigned int)nkb);
-        fresh->pattern.insert(fresh->pattern.end(), hc, hc + n_ptr); fresh->pattern.insert(fresh->pattern.end(), hr, hr + nnzb);
-        fresh->d_block = blockp;
-        if (nkb <= 64 && a.bn > 0)        // the k-blocks the first 64 columns use (see BcscArgs::kmask0)
-          for (unsigned long long nb = 0; nb < nblk_n && nb * (unsigned long long)a.bn < 64ull; ++nb)
-            for (unsigned int b = hc[nb]; b < hc[nb + 1]; ++b) fresh->kmask0 |= 1ull << hr[b];
-        // an evicted entry stays alive until the kernel is released: another thread may be past its lock-free hit, a launch may still read its table
-        if (k->bcsc_cache.size() >= 4) { k->bcsc_old.push_back(k->bcsc_cache.front()); k->bcsc_cache.erase(k->bcsc_cache.begin()); }
-        // ... but a caller that cycles through many patterns must not grow device memory without bound (advisor, round 3): beyond 64 retired entries that still own a device table the
-        // tables of the oldest 32 are freed after the device has drained (no launch can still read them; a thread would have to sit between its lock-free hit and
-        // its launch across 32 pattern insertions for the pointer to matter).  The small host parts stay until the kernel is released.
-        size_t live_old = 0;
-        for (auto* e : k->bcsc_old) live_old += e->d_block ? 1 : 0;
-        if (live_old > 64) {
-          (void)hipDeviceSynchronize();
-          size_t freed = 0;
-          for (auto* e : k->bcsc_old) { if (freed == 32) break; if (e->d_block) { (void)hipFree(e->d_block); e->d_block = nullptr; ++freed; } }
-        }
-        k->bcsc_cache.push_back(fresh);
-        k->device = cur_device();
-        hit = fresh;
-      }
-      k->bcsc_last.store(hit, std::memory_order_release);
-    }
+    const size_t n_ptr = (size_t)nblk_n + 1, n_idx = std::max<size_t>(1, nnzb);
     unsigned int* blockp = hit->d_block;
     a.colptr = blockp; a.rowidx = blockp + n_ptr; a.table = blockp + n_ptr + n_idx; a.table_ready = 1; a.nnzb = (int)nnzb; a.kmask0 = hit->kmask0;
   } else {
-  a.colptr = (const unsigned int*)device_visible(p->b.secondary, (size_t)(nblk_n + 1) * sizeof(unsigned int));
-  if (!a.colptr) { set_error(-2, "BCSC kernel needs colptr in b.secondary"); return; }
-  // rowidx: a device array is used in place (no size needed, no host round trip -> capturable in a hipGraph); a host
-  // array is staged, its length colptr[nblk_n] being host-readable in that case
-  {
-    const bool idx_on_device = (hipPointerGetAttributes(&attr, p->b.tertiary) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged));
-    (void)hipGetLastError();
-    if (idx_on_device) a.rowidx = (const unsigned int*)p->b.tertiary;
+    a.colptr = (const unsigned int*)device_visible(p->b.secondary, (size_t)(nblk_n + 1) * sizeof(unsigned int));
+    if (!a.colptr) { set_error(-2, "BCSC kernel needs colptr in b.secondary"); return; }
+    // rowidx: a device array is used in place (no size needed, no host round trip -> capturable in a hipGraph); a host
+    // array is staged, its length colptr[nblk_n] being host-readable in that case
+    const hipMemoryType idx_at = pointer_type(p->b.tertiary);
+    if (idx_at == hipMemoryTypeDevice || idx_at == hipMemoryTypeManaged) a.rowidx = (const unsigned int*)p->b.tertiary;
     else {
-      const bool ptr_on_device = (hipPointerGetAttributes(&attr, p->b.secondary) == hipSuccess && attr.type == hipMemoryTypeDevice);
-      (void)hipGetLastError();
       unsigned int nnzb = 0;
-      if (!ptr_on_device) nnzb = ((const unsigned int*)p->b.secondary)[nblk_n];
+      if (pointer_type(p->b.secondary) != hipMemoryTypeDevice) nnzb = ((const unsigned int*)p->b.secondary)[nblk_n];
       else { (void)hipMemcpyAsync(&nnzb, (const unsigned int*)p->b.secondary + nblk_n, sizeof(nnzb), hipMemcpyDeviceToHost, cur_stream()); (void)hipStreamSynchronize(cur_stream()); }
       a.rowidx = (const unsigned int*)device_visible(p->b.tertiary, (size_t)std::max(1u, nnzb) * sizeof(unsigned int));
     }
-  }
-  const KernelCtx::BcscBound& bd = k->bcsc_bound;
-  if (nkb > 0 && bd.d_table && bd.colptr == p->b.secondary && bd.rowidx == p->b.tertiary && bd.nblk_n == nblk_n && bd.nkb == nkb) {
-    a.table = bd.d_table; a.table_ready = 1;        // libxsmm_hip_bcsc_bind_pattern: inverted once, no inversion kernel per call
-    a.nnzb = bd.nnzb; a.kmask0 = bd.kmask0;         // ... and read once: the streaming kernels that keep B in LDS apply as for a host-resident pattern
-  } else if (nkb > 0) a.table = workspace((size_t)std::max(1, a.nblk_n) * (size_t)nkb * sizeof(unsigned int));
+    const KernelCtx::BcscBound& bd = k->bcsc_bound;
+    if (nkb > 0 && bd.d_table && bd.colptr == p->b.secondary && bd.rowidx == p->b.tertiary && bd.nblk_n == nblk_n && bd.nkb == nkb) {
+      a.table = bd.d_table; a.table_ready = 1;        // libxsmm_hip_bcsc_bind_pattern: inverted once, no inversion kernel per call
+      a.nnzb = bd.nnzb; a.kmask0 = bd.kmask0;         // ... and read once: the streaming kernels that keep B in LDS apply as for a host-resident pattern
+    } else if (nkb > 0) a.table = workspace((size_t)std::max(1, a.nblk_n) * (size_t)nkb * sizeof(unsigned int));
   }
   if (!a.a || !a.bvals || !a.c || !a.rowidx) { set_error(-2, "BCSC kernel called with a NULL operand"); return; }
   const char* kname = nullptr;

@@ -189,9 +189,9 @@ def test_a_result_in_an_empty_column_that_is_not_exactly_its_start_value_is_reje
 
 
 def test_every_bcsc_kernel_name_in_the_source_has_a_row_or_a_reason():
-    """Every quoted bcsc_*_kernel name string of csrc/sparse_kernels.hip is the expected name of a row of BCSC (asserted there by name on the GPU) or is listed in
-    UNREACHABLE with the reason: a kernel name added to launch_bcsc fails here until it has one or the other."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "libxsmm_amd", "csrc", "sparse_kernels.hip")
+    """Every quoted bcsc_*_kernel name string of csrc/bcsc_plan.hpp is the expected name of a row of BCSC (asserted there by name on the GPU) or is listed in
+    UNREACHABLE with the reason: a kernel name added to plan_bcsc fails here until it has one or the other."""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "libxsmm_amd", "csrc", "bcsc_plan.hpp")
     names = set(re.findall(r'"(bcsc_[a-z0-9_]+_kernel)"', open(path).read()))
     assert len(names) >= 11, sorted(names)
     rows = {k for k, _ in BCSC}

@@ -1,12 +1,13 @@
-"""Block-sparse (BCSC) GEMM, every kernel launch_bcsc can pick, held per element against a float64 restatement (tests/bcsc_parity_helpers.py).
+"""Block-sparse (BCSC) GEMM, every kernel plan_bcsc can pick and launch_bcsc then launches, held per element against a float64 restatement (tests/bcsc_parity_helpers.py).
 
-BCSC is a table of (expected kernel name, case) rows.  The name of every row is derived from the conditions of launch_bcsc / run_bcsc (csrc/sparse_kernels.hip,
-csrc/runtime.cpp) and says in its comment which one it exercises; the test asserts libxsmm_hip_kernel_name, every element of every M-block against
+BCSC is a table of (expected kernel name, case) rows.  The name of every row is derived from the conditions of plan_bcsc / run_bcsc (csrc/bcsc_plan.hpp,
+csrc/runtime.cpp) and says in its comment which one it exercises (tests/test_bcsc_plan_cpu.py holds the plan alone to the same names, without a GPU); the test
+asserts libxsmm_hip_kernel_name, every element of every M-block against
 gemm_ld_helpers.bound64, and every margin around A, B's values and C bit for bit.  Data: bcsc_parity_helpers.wide (17 binades, full significands, exact zeros),
 full-range bytes for the integer kernels; every M-block has its own A.  Patterns carry a block column with every k-block, one with none and one stored in
 descending order (edge_columns), written out where a row needs a particular size of B.
 
-The conditions, for reference (nbl = 64 / bn n-blocks per wave, nkb = K / bk, tiles = ceil(M / 64) ceil(N / 64)):
+The conditions, as plan_bcsc states them (nbl = 64 / bn n-blocks per wave, nkb = K / bk, tiles = ceil(M / 64) ceil(N / 64)):
   matrix cores   bf16: VNNI-2 A, bk % 32 == 0;  f32: bk % 16 == 0;  i8: VNNI-4 A, bk % 32 == 0;  all: bn in {16, 32, 64}, M % 16 == 0, nbl nkb <= 1024,
                  A % 4 == 0, values of B % 16 == 0 (i8: % 8), C % 16 == 0 -- else bcsc_generic_kernel
   LDS-DMA        nbl nkb <= 256 and A % 16 == 0 -- else the register kernels (bcsc_mfma_bf16_kernel / _i8_kernel; f32 has no dma kernel: bcsc_mfma_f32_kernel)
