@@ -291,8 +291,8 @@ LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan
  * result is the k-ordered fmaf chain bit for bit.  A segment of count 0 is the reference's call with a count of 0: beta = 0 sets the m x n block to +0,
  * beta = 1 leaves it untouched.  Work is handed to the device in list order (a work item is a segment's C tile, taken up in ascending order): a caller who
  * lists long segments first gets longest-first scheduling for free; a segment is never split, which would reorder its sum.
- * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16, BF8 x BF8 -> f32 / BF8, HF8 x HF8 -> f32 / HF8 (comp f32); A flat (or
- * VNNI_A for bf16; for the 8-bit floats VNNI_A is required: A is taken as VNNI-4 only, A(i,k) at ((k / 4) * lda + i) * 4 + k % 4, k a multiple of 4), B flat,
+ * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16, F16 x F16 -> f32 / F16, BF8 x BF8 -> f32 / BF8, HF8 x HF8 -> f32 / HF8
+ * (comp f32); A flat (or VNNI_A for bf16 and f16; for the 8-bit floats VNNI_A is required: A is taken as VNNI-4 only, A(i,k) at ((k / 4) * lda + i) * 4 + k % 4, k a multiple of 4), B flat,
  * C not VNNI, no transposes; beta 0 or 1; no flag beyond those and the hints; any m, n, k and leading dimensions whose element offsets inside an operand stay
  * below 2^31.  Block pointers need element alignment only (8-bit floats: any byte).
  * 8-bit floats (BF8 = E5M2, HF8 = E4M3) [ref: src/generator_gemm_reference_impl.c:2420-2510, own-type C :2511-2619]: per segment one f32 accumulator over
@@ -300,11 +300,20 @@ LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan
  * the library's two-step conversion f32 -> f16 -> 8 bits, NaNs in software -- the conversion the dense 8-bit float kernels store with.  A count of 0 stores
  * beta * C (for an 8-bit C the round trip of the byte: the identity on every code that is not a NaN).  Bytes of C outside m x n stay the caller's.  The matrix
  * core (v_mfma_f32_32x32x16_{bf8_bf8,fp8_fp8}, v_mfma_f32_16x16x32_*) aligns the products of one instruction before it adds them, so the result is the
- * reference's serial chain within a tolerance -- bitwise where every partial sum is exact -- like the dense 8-bit float kernels.  Follows the thread's launch mode: blocking (returns when done), stream-ordered, coalescing (the queue is flushed first),
+ * reference's serial chain within a tolerance -- bitwise where every partial sum is exact -- like the dense 8-bit float kernels.
+ * IEEE halves (F16 x F16 -> f32 / F16, any comp type but F16; A flat or VNNI-2 -- the bf16 image --, B and C flat) follow the reference's F16 loop, which is
+ * NOT the bf16 rule [ref: src/generator_gemm_reference_impl.c:2025-2124]: per element the sum is one f32 chain over (product, k) in list order STARTED AT +0
+ * (v_mfma_f32_32x32x16_f16 / v_mfma_f32_16x16x16_f16: the products, exact in f32, are added in the instruction's order -- bitwise the reference where every
+ * partial sum is exact, within a tolerance otherwise); then, under beta = 1, C is ROUNDED TO A HALF, widened and added to the sum in one f32 add -- the
+ * identity for an f16 C, a real rounding for an f32 C; then one store, an f32 C as it is, an f16 C through the hardware's round-to-nearest-even conversion.
+ * A count of 0 under beta = 1 therefore stores f16(C) widened: for an f32 C NOT C's own bits, unlike every other class.  comp type F16 (the running sum
+ * rounded to a half after every product) is refused with -3: only the dense generic kernel does that.  No f16 handle has TRANS_A (libxsmm_dispatch_brgemm
+ * returns NULL, as the reference's F16 loop has no transposed A).
+ * Follows the thread's launch mode: blocking (returns when done), stream-ordered, coalescing (the queue is flushed first),
  * inside a pipeline section (the launch goes to a lane).  Errors are set before anything is launched.  -2: param, seg_ptr, a_list, b_list or c_list is NULL
  * while nsegments > 0; -3: an unknown handle, a TPP / equation / sparse / ext handle, a GEMM handle that is not ADDRESS batch-reduce, or a type, layout or
  * flag outside the list above (the message names which); -4: no device.  nsegments = 0 does nothing.  libxsmm_hip_kernel_name(kernel, 1) names the
- * kernel that ran (gemm_segments_f32_kernel, _f64_kernel, _bf16_kernel, _bf8_kernel, _hf8_kernel).
+ * kernel that ran (gemm_segments_f32_kernel, _f64_kernel, _bf16_kernel, _f16_kernel, _bf8_kernel, _hf8_kernel).
  */
 LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction kernel, const libxsmm_gemm_param* param,
   size_t nsegments, const unsigned long long* seg_ptr, const void* const* a_list, const void* const* b_list, void* const* c_list);
@@ -328,7 +337,10 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments(libxsmm_gemmfunction ker
  * Eligible handles: ADDRESS batch-reduce ext handles under the plain entry's type, layout and flag rules (f32 -> f32, bf16 -> f32 / bf16; A flat or VNNI-2,
  * B flat, C not VNNI, NN; beta 0 or 1; the hints; element offsets below 2^31) with BINARY_ADD + BCAST_COL_IN_0/1, cp RELU (with or without bitmask), cp
  * SIGMOID, or no operator at all -- an ext handle without operators is taken for f64 and for the 8-bit floats (BF8 / HF8 -> f32 / own type, A VNNI-4) as well
- * and runs the plain kernels; an 8-bit float ext handle with a bias or an activation is refused ("taken without operators only").  Errors are set before
+ * and runs the plain kernels; an 8-bit float ext handle with a bias or an activation is refused ("taken without operators only").  F16 -> f32 / F16 ext
+ * handles are taken with every operator of the list (gemm_segments_f16_fused_kernel), the bias having C's type, under the F16 rule of the plain entry
+ * [ref: src/generator_gemm_reference_impl.c:296-317 with :2112-2117]: the sum runs from +0; the start value -- C, the bias, or bias + C in one f32 add -- is
+ * rounded to a half, widened and added behind it; then mask, activation and store.  A segment of count 0 stores the activation of f16(start).  Errors are set before
  * anything is launched.  -2: param, seg_ptr, a_list, b_list or c_list is NULL while nsegments > 0; a bias handle with d_list and param->d.primary both NULL; a bitmask
  * handle with mask_list NULL.  -3: an unknown handle, a non-ext / TPP / equation / sparse handle, a handle that is not ADDRESS batch-reduce, a type, layout,
  * flag or operator outside the list (the message names which).  -4: no device.  nsegments = 0 does nothing.  Follows the thread's launch mode like the plain
@@ -356,7 +368,9 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments(libxsmm_gemmfunction
  * chain over (product, k) in list order from C (beta = 1) or +0; a segment of count 0 stores beta * C; for f32 the result is the k-ordered fmaf chain bit for
  * bit, in every form.  Work is handed out in list order; a segment is never split.
  * Eligible handles: f32 x f32 -> f32, f64 x f64 -> f64, bf16 x bf16 -> f32 / bf16; BF8 x BF8 -> f32 / BF8 and HF8 x HF8 -> f32 / HF8 NN only, A VNNI-4
- * (LIBXSMM_GEMM_FLAG_VNNI_A required, TRANS_A / TRANS_B refused), with the semantics given at libxsmm_hip_gemm_batch_reduce_segments.  A flat, A with TRANS_A (flat, A(i,k) at i * lda + k, lda >= k) or, for
+ * (LIBXSMM_GEMM_FLAG_VNNI_A required, TRANS_A / TRANS_B refused), with the semantics given at libxsmm_hip_gemm_batch_reduce_segments; F16 x F16 -> f32 / F16
+ * (comp type not F16) NN and NT, A flat or VNNI-2, with the F16 rule given there (the sum from +0, f16(C) added behind it; a count of 0 under beta = 1 stores
+ * f16(C) widened) -- no f16 handle with TRANS_A exists, so TN / TT cannot be asked for (gemm_segments_offs_f16_kernel<0,tb>).  A flat, A with TRANS_A (flat, A(i,k) at i * lda + k, lda >= k) or, for
  * bf16, VNNI-2 without TRANS_A; B flat or B with TRANS_B (flat, B(k,j) at k * ldb + j, ldb >= n); both transposes together are allowed; VNNI_B and VNNI_C are
  * refused; beta 0 or 1; no flag beyond those and the hints; element offsets inside one operand (lda * m and ldb * k for transposed ones) stay below 2^31.
  * Offsets need element alignment only.  Follows the thread's launch mode: blocking, stream-ordered, coalescing (the queue is flushed first), inside a pipeline
@@ -396,7 +410,9 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets(libxsmm_gemmfunc
  * Eligible handles: every handle the plain offsets entry takes, made into an ext handle -- f32 -> f32, bf16 -> f32 / bf16; A flat, TRANS_A or (bf16, without
  * TRANS_A) VNNI-2; B flat or TRANS_B; NN, TN, NT and TT; beta 0 or 1; the hints; element offsets below 2^31 -- with BINARY_ADD + BCAST_COL_IN_0/1, cp RELU (with
  * or without bitmask), cp SIGMOID, or no operator at all: an ext handle without operators is taken for f64 as well and runs the plain offsets kernels; f64 with
- * operators is refused; the same holds for the 8-bit floats (NN, A VNNI-4: without operators the plain offsets kernels, with operators refused).  Errors are
+ * operators is refused; the same holds for the 8-bit floats (NN, A VNNI-4: without operators the plain offsets kernels, with operators refused).  F16 -> f32 /
+ * F16 ext handles (NN, NT) are taken with every operator, under the F16 rule of libxsmm_hip_gemm_ext_batch_reduce_segments: the start value is rounded to a
+ * half and added behind the sum (gemm_segments_offs_f16_fused_kernel<0,tb>).  Errors are
  * set before anything is launched, one per refusal.  -2: param, seg_ptr, a_offs, b_offs, c_offs or one of the three bases is
  * NULL while nsegments > 0; a bias handle with param->d.primary NULL; a bitmask handle with mask_offs or param->c.secondary NULL.  -3: an unknown handle, a
  * non-ext / TPP / equation / sparse handle, a handle that is not OFFSET batch-reduce, a type, layout, flag or operator outside the list (the message names
@@ -424,6 +440,10 @@ LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_offsets(libxsmm_gemm
  * denormals kept; acc is stored with one rounding through the library's bf16 conversion for a bf16 C.  Bytes of the C block outside m x n stay the caller's.
  * 8-bit float handles (BF8 / HF8, A VNNI-4, NN): the partials are f32, started at +0; pass 2 adds them in ascending slice order to C widened to f32 or to +0
  * and stores once -- an f32 C as it is, an 8-bit C through the two-step conversion of the unsliced entries; the workspace holds 4-byte accumulators.
+ * F16 handles: the partials are f32 from +0 (4-byte accumulators); pass 2 is acc = +0, acc += P_j in ascending slice order, THEN acc += f16(C) widened
+ * (beta = 1), then one store (gemm_segments_slice_reduce_kernel<5> for an f16 C, <6> for an f32 C under beta = 1, <0> under beta = 0).  The start value comes
+ * last here and in the unsliced entries, so for f16 one slice per block is bitwise the unsliced call FOR EVERY BETA.  A block without slices keeps the rule
+ * below: under beta = 1 it is untouched, so an f32 C is not rounded there.
  * A block with no slices: beta = 0 stores +0, beta = 1 leaves the block untouched.  Consequences: with beta = 0 and one slice per block the result is bitwise
  * the unsliced call's (a chain started at +0 never yields -0, so +0 + P is P); with beta = 1 the original C is ADDED TO the first partial, not used as the
  * chain's start -- the documented difference from the unsliced entries, as in ORDER_ANY.  Blocks whose C overlaps are undefined; A and B blocks may be shared.
@@ -497,6 +517,10 @@ LIBXSMM_API void libxsmm_hip_gemm_batch_reduce_segments_offsets_sliced(libxsmm_g
  * launch mode like the siblings.  A call is TWO launches in order on one stream or pipeline lane (with nslices = 0 the first is skipped);
  * libxsmm_hip_launch_count counts both; libxsmm_hip_kernel_name(kernel, 1) names the first, the plain sliced entries' kernels, reused as they are; the second
  * is gemm_segments_slice_reduce_fused_kernel<0> (f32 C) or <1> (bf16 C).  DESIGN.md section 9.6 has the mask scheme and the measurements.
+ * F16 -> f32 / F16 ext handles (pass 2: instances <5> for an f16 C, <6> for an f32 C) take the start value LAST, as their unsliced entries do: acc = +0;
+ * acc += P_j ascending; then the start value -- C, the bias of C's type, or bias + C in one f32 add --, rounded to a half and widened, is added in one f32
+ * add (nothing without a start); then mask, activation, store.  So one slice per block is bitwise the unsliced ext call for every beta and with a bias --
+ * for the other classes only under beta = 0 without a bias -- and a block without slices is the unsliced segment of count 0.
  */
 LIBXSMM_API size_t libxsmm_hip_gemm_ext_batch_reduce_segments_sliced_workspace(libxsmm_gemmfunction_ext kernel, size_t nslices);
 LIBXSMM_API void libxsmm_hip_gemm_ext_batch_reduce_segments_sliced(libxsmm_gemmfunction_ext kernel, const libxsmm_gemm_ext_param* param,

@@ -12,6 +12,10 @@
 //   f32 : v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 with k in natural order -- the result is the k-ordered fmaf chain bit for bit
 //         (cdna_hip_programming.md, "FP32-input MFMA"), which is what oracle_gemm_f32_fma computes [ref: src/generator_gemm_reference_impl.c:1359-1426].
 //   bf16: v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x16_bf16, A flat or VNNI-2, B flat, C f32 or bf16 (bf16_cvt.hpp: the reference's conversion exactly).
+//   f16 : v_mfma_f32_32x32x16_f16 / v_mfma_f32_16x16x16_f16 through the bf16 tile (template argument H16: same lane layout, same loads, same padding -- 0x8000 is
+//         -0 and 0 is +0 in both formats), A flat or VNNI-2, B flat, C f32 or f16.  The start rule is the reference's F16 loop, NOT the bf16 one
+//         [ref: src/generator_gemm_reference_impl.c:2025-2124, :296-317]: the chain starts at +0, the start value (C, the bias, bias + C in one f32 add) is
+//         rounded to f16, widened and added AFTER the sum in one f32 add; an f16 C leaves through the hardware RNE conversion (cvt_pk_f16).
 //   f64 : v_mfma_f64_16x16x4_f64, T = 16 only, k in natural order, four k per instruction [ref: src/generator_gemm_reference_impl.c:1322-1358].
 //   fp8 : v_mfma_f32_32x32x16_{bf8_bf8,fp8_fp8} / v_mfma_f32_16x16x32_{bf8_bf8,fp8_fp8} (BF8 = E5M2, HF8 = E4M3), A VNNI-4, B flat, NN only, C f32 or the
 //         operands' type (gemm_8bit.hpp: the reference's two-step rounding) [ref: src/generator_gemm_reference_impl.c:2420-2619].  The matrix core aligns the
@@ -120,9 +124,14 @@ struct FusedEpilogue {
 
 // the accumulator's start value: C (beta = 1) or +0; fused: bias, or bias + C in one f32 add.  C8 (the 8-bit float tiles only: 1 BF8, 2 HF8): C is f32 or,
 // with g.c_kind >= 2, of the operands' type and widened; the other instances know c_kind as 0 or 1 and keep the code they had with a single bf16 bit.
-template <int T, typename Epi = NoEpilogue, int C8 = 0>
+// H16 (the f16 tiles only): the chain starts at +0 and nothing is loaded -- the start value is added behind the sum, in acc_store.
+template <int T, typename Epi = NoEpilogue, int C8 = 0, bool H16 = false>
 __device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& g, gptr c, int i, int j0, bool mv, unsigned int lane, const Epi& e = Epi()) {
   typename Acc<T>::type acc;
+  if constexpr (H16) {
+    static_for<Acc<T>::N>([&](auto r) { acc[r.value] = 0.0f; });
+    return acc;
+  }
   float bias = 0.0f;
   bool biased = false;
   if constexpr (Epi::fused) {
@@ -151,7 +160,10 @@ __device__ __forceinline__ typename Acc<T>::type acc_start(const GemmGroupDesc& 
 // ReLU bitmask of one tile: bit i % 8 of byte i / 8 + j * (mask_ld / 8) is !(x <= 0) of the sum [ref: mateltwise ref :150-157, :2142].  The lanes hold rows,
 // so a register's ballot is the mask of its two (T = 32) or four (T = 16) columns; the lane with (lane & 7) == 0 owns the byte of its 8 rows.  Tile origins are
 // multiples of 16: a byte never straddles tiles.  Only bits of rows < m, columns < n change: the byte that holds row m - 1 is read, merged and written back.
-template <int T>
+// (H16: the f16 tiles take an instance of their own.  The body is the same; sharing one instance -- and so one lambda, the one function here that the
+// inliner weighs -- with more callers changed the register allocation of the existing fused kernels.  Marking the lambda always_inline instead was tried: it
+// changes the code of the ten existing fused segment kernels too, so it would have to come with a re-measurement of those; tools/code_diff.py is the check.)
+template <int T, bool H16 = false>
 __device__ __forceinline__ void acc_relu_mask(const GemmGroupDesc& g, const FusedEpilogue& e, const typename Acc<T>::type& acc, int i, int j0, bool mv, unsigned int lane) {
   static_for<Acc<T>::N>([&](auto r) {
     const int j = j0 + acc_col<T>(r, lane);
@@ -166,9 +178,58 @@ __device__ __forceinline__ void acc_relu_mask(const GemmGroupDesc& g, const Fuse
   });
 }
 
-template <int T, typename Epi = NoEpilogue, int C8 = 0>
+// H16 (the f16 tiles only; g.c_kind == 4: C and the bias are f16, else f32): `acc` is the sum from +0.  The start value -- C under beta = 1, the bias, or
+// bias + C in one f32 add -- is loaded here under the predicates of the stores (i < m, j < n; the bias row clamped to m - 1 as in acc_start), rounded to f16
+// (the identity for a lone f16 value, a real rounding for an f32 C, an f32 bias or a sum), widened and added in one f32 add; without a start nothing is added.
+// Then mask, activation and store as for every class; an f16 C is converted two results at a time (v_cvt_pk_f16_f32: RNE, registers 2 q and 2 q + 1 are two
+// columns of the lane's row) and stored element by element, as the bf16 C is.
+template <int T, typename Epi = NoEpilogue, int C8 = 0, bool H16 = false>
 __device__ __forceinline__ void acc_store(const GemmGroupDesc& g, gptr c, typename Acc<T>::type acc, int i, int j0, bool mv, unsigned int lane, const Epi& e = Epi()) {
   constexpr int N = Acc<T>::N;
+  if constexpr (H16) {
+    const bool c16 = g.c_kind == 4;
+    float bias = 0.0f;
+    bool biased = false;
+    if constexpr (Epi::fused) {
+      biased = e.colbias != 0;
+      if (biased) {
+        const int il = min(i, g.m - 1);
+        bias = c16 ? (float)((GM const _Float16*)e.d)[il] : ((GM const float*)e.d)[il];
+      }
+    }
+    if (g.beta1 || biased) {
+      static_for<N>([&](auto r) {
+        const int j = j0 + acc_col<T>(r, lane);
+        float v = 0.0f;
+        if (g.beta1 && mv && j < g.n) {
+          const long long o = (long long)j * g.ldc + i;
+          v = c16 ? (float)((GM const _Float16*)c)[o] : ((GM const float*)c)[o];
+        }
+        if (biased) v = g.beta1 ? bias + v : bias;
+        acc[r.value] = acc[r.value] + (float)(_Float16)v;
+      });
+    }
+    if constexpr (Epi::fused) {
+      if (e.act == 2) acc_relu_mask<T, true>(g, e, acc, i, j0, mv, lane);
+      if (e.act == 3) static_for<N>([&](auto r) { acc[r.value] = act_fixed<3>(acc[r.value]); });
+      else if (e.act != 0) static_for<N>([&](auto r) { acc[r.value] = act_fixed<1>(acc[r.value]); });
+    }
+    if (c16) {
+      static_for<N / 2>([&](auto q) {
+        constexpr int r0 = 2 * q.value, r1 = r0 + 1;
+        const unsigned int w = cvt_pk_f16(acc[r0], acc[r1]);
+        const int ja = j0 + acc_col<T>(r0, lane), jb = j0 + acc_col<T>(r1, lane);
+        if (mv && ja < g.n) ((GM unsigned short*)c)[(long long)ja * g.ldc + i] = (unsigned short)(w & 0xffffu);
+        if (mv && jb < g.n) ((GM unsigned short*)c)[(long long)jb * g.ldc + i] = (unsigned short)(w >> 16);
+      });
+    } else {
+      static_for<N>([&](auto r) {
+        const int j = j0 + acc_col<T>(r, lane);
+        if (mv && j < g.n) ((GM float*)c)[(long long)j * g.ldc + i] = acc[r.value];
+      });
+    }
+    return;
+  }
   if constexpr (Epi::fused) {                      // the mask from the sums, then the activation, then the store below
     if (e.act == 2) acc_relu_mask<T>(g, e, acc, i, j0, mv, lane);
     if (e.act == 3) static_for<N>([&](auto r) { acc[r.value] = act_fixed<3>(acc[r.value]); });
@@ -293,11 +354,21 @@ template <> struct Frag<8> { typedef bf16x8 type; typedef u32x4 words; };
 template <> struct Frag<4> { typedef bf16x4 type; typedef u32x2 words; };
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 x, bf16x8 y, f32x16 acc) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma_bf16(bf16x4 x, bf16x4 y, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(x, y, acc, 0, 0, 0); }
+// the same steps on IEEE halves (H16): v_mfma_f32_32x32x16_f16 / v_mfma_f32_16x16x16_f16 take the operands of their bf16 siblings lane for lane
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+template <bool H16> __device__ __forceinline__ f32x16 mfma_16(bf16x8 x, bf16x8 y, f32x16 acc) {
+  if constexpr (H16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, x), __builtin_bit_cast(f16x8_t, y), acc, 0, 0, 0);
+  else return mfma_bf16(x, y, acc);
+}
+template <bool H16> __device__ __forceinline__ f32x4 mfma_16(bf16x4 x, bf16x4 y, f32x4 acc) {
+  if constexpr (H16) return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, x), __builtin_bit_cast(f16x4_t, y), acc, 0, 0, 0);
+  else return mfma_bf16(x, y, acc);
+}
 // U consecutive MFMA steps (16 k each) of a bf16 tile from k = kk on, every operand request ahead of the first MFMA; VEC: both operands are known to take
 // the wide loads (no element-wise code in the instance)
 // TA: `ap` is the lane's row of a transposed A and a step is ONE 16- / 8-byte load of its k run under a_vec (B's form); TB: `bp` is the lane's column of a
 // transposed B, read element by element at k * ldb (flat A's form)
-template <int T, int U, bool VEC, bool TA = false, bool TB = false> __device__ __forceinline__ void steps_bf16(const GemmGroupDesc& g, typename Acc<T>::type& acc, GM const unsigned short* ap, GM const unsigned short* bp,
+template <int T, int U, bool VEC, bool TA = false, bool TB = false, bool H16 = false> __device__ __forceinline__ void steps_bf16(const GemmGroupDesc& g, typename Acc<T>::type& acc, GM const unsigned short* ap, GM const unsigned short* bp,
   int kk, int il, int h, bool a_vec, bool b_vec) {
   constexpr int E = (T == 32) ? 8 : 4, KS = 16;
   typedef typename Frag<E>::type frag;
@@ -332,9 +403,10 @@ template <int T, int U, bool VEC, bool TA = false, bool TB = false> __device__ _
     }
   }
 #pragma unroll
-  for (int u = 0; u < U; ++u) acc = mfma_bf16(x[u], y[u], acc);
+  for (int u = 0; u < U; ++u) acc = mfma_16<H16>(x[u], y[u], acc);
 }
-template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue, bool TA = false, bool TB = false>
+// H16: the elements are IEEE halves -- the f16 instructions, and the f16 start rule of acc_start / acc_store; everything else is the bf16 tile
+template <int T, bool DEEP, typename Chain, typename Epi = NoEpilogue, bool TA = false, bool TB = false, bool H16 = false>
 __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& ch, gptr c, int i0, int j0, unsigned int lane, const Epi& e = Epi()) {
   constexpr int E = (T == 32) ? 8 : 4, KS = 16;
   typedef typename Frag<E>::type frag;
@@ -342,7 +414,7 @@ __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& c
   const int i = i0 + lr, j = j0 + lr;
   const bool mv = i < g.m;
   const int il = min(i, g.m - 1);
-  typename Acc<T>::type acc = acc_start<T, Epi>(g, c, i, j0, mv, lane, e);
+  typename Acc<T>::type acc = acc_start<T, Epi, 0, H16>(g, c, i, j0, mv, lane, e);
   const int K = g.k;
   const int kbig = K - K % (4 * KS), kfull = K - K % KS;
   gcptr an = nullptr, bn = nullptr;
@@ -358,9 +430,9 @@ __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& c
     if constexpr (TA) a_vec = (T == 32) ? ch.a_vec16(a) : ch.a_vec8(a); else a_vec = g.vnni_a && ch.a_vec4(a);
     int kk = 0;
     if constexpr (DEEP && !TB) {               // segments: 64 k per round of requests when both operands take the wide loads (32 more registers)
-      if (a_vec && b_vec) for (; kk < kbig; kk += 4 * KS) steps_bf16<T, 4, true, TA, TB>(g, acc, ap, bp, kk, il, h, true, true);
+      if (a_vec && b_vec) for (; kk < kbig; kk += 4 * KS) steps_bf16<T, 4, true, TA, TB, H16>(g, acc, ap, bp, kk, il, h, true, true);
     }
-    for (; kk < kfull; kk += KS) steps_bf16<T, 1, false, TA, TB>(g, acc, ap, bp, kk, il, h, a_vec, b_vec);
+    for (; kk < kfull; kk += KS) steps_bf16<T, 1, false, TA, TB, H16>(g, acc, ap, bp, kk, il, h, a_vec, b_vec);
     if (kk < K) {                              // ragged k: A = -0 (0x8000), B = +0 beyond K
       const int k0 = kk + E * h;
       frag x, y;
@@ -373,10 +445,10 @@ __device__ __forceinline__ void tile_bf16(const GemmGroupDesc& g, const Chain& c
         x[e] = (short)(kx < K ? vb : 0);
         y[e] = (short)(kx < K ? va : 0x8000);
       }
-      acc = mfma_bf16(x, y, acc);
+      acc = mfma_16<H16>(x, y, acc);
     }
   }
-  acc_store<T, Epi>(g, c, acc, i, j0, mv, lane, e);
+  acc_store<T, Epi, 0, H16>(g, c, acc, i, j0, mv, lane, e);
 }
 
 // 8-bit floats (HF8: E4M3, else BF8 = E5M2): lane (i = lane % T, h = lane / T) feeds A(i, k0 + 8 h + e) and B(k0 + 8 h + e, j0 + lane % T), e < 8, per MFMA -- 8

@@ -34,6 +34,11 @@
 // 8-bit floats (classes 3 BF8 and 4 HF8): BF8 x BF8 -> f32 / BF8 and HF8 x HF8 -> f32 / HF8 through tile_fp8 (gemm_group_tile.hpp) in the
 // plain ADDRESS, OFFSET and sliced kernels -- A VNNI-4, NN only, so the offsets kernels have the <0,0> instance alone; never fused.  Pass 2 stores an 8-bit C
 // through the instances <3> / <4> of gemm_segments_slice_reduce_kernel.
+// IEEE halves (class 5): F16 x F16 -> f32 / f16 through tile_bf16 with the f16 instructions (gemm_group_tile.hpp, H16) in EVERY kernel
+// family bf16 has -- ADDRESS, OFFSET, fused, sliced.  The offsets kernels exist as <0,0> (NN) and <0,1> (NT) only: libxsmm_dispatch_brgemm returns no f16
+// handle with TRANS_A, because the reference's F16 loop has no transposed A [ref: src/generator_gemm_reference_impl.c:2049], so TN / TT cannot be asked for.  The arithmetic is the reference's F16 loop, not bf16's: the chain runs from +0 and the
+// start value (C, the bias, bias + C), rounded to a half, is added behind it.  So a segment of count 0 under beta = 1 stores f16(C) widened -- for an f32 C NOT
+// C's own bits, unlike every other class -- and one slice per block is the unsliced call bit for bit for every beta and with a bias.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "internal.hpp"
@@ -88,11 +93,15 @@ struct OffsetSegEpilogue {
   }
 };
 
-// CLS: 0 f32, 1 bf16, 2 f64 (16 x 16 tiles only, no epilogue), 3 BF8, 4 HF8 (NN only, no epilogue; C f32 or the operands' type).  The tile edge is a
-// wave-uniform runtime value, the class and the transposes pick the instance.
+// CLS: 0 f32, 1 bf16, 2 f64 (16 x 16 tiles only, no epilogue), 3 BF8, 4 HF8 (NN only, no epilogue; C f32 or the operands' type), 5 f16 (everything bf16
+// takes; C f32 or f16).  The tile edge is a wave-uniform runtime value, the class and the transposes pick the instance.
 template <int CLS, bool TA, bool TB, typename Chain, typename Epi>
 __device__ __forceinline__ void segment_tile(const GemmGroupDesc& g, const Chain& ch, gptr c, int tm, int tn, unsigned int lane, const Epi& e) {
   if constexpr (CLS == 2) tile_f64<Chain, TA, TB>(g, ch, c, tm * 16, tn * 16, lane);
+  else if constexpr (CLS == 5) {                   // IEEE halves: the bf16 tile with the f16 instructions and the f16 start rule
+    if (g.tile == 32) tile_bf16<32, true, Chain, Epi, TA, TB, true>(g, ch, c, tm * 32, tn * 32, lane, e);
+    else tile_bf16<16, true, Chain, Epi, TA, TB, true>(g, ch, c, tm * 16, tn * 16, lane, e);
+  }
   else if constexpr (CLS >= 3) {
     static_assert(!TA && !TB && !Epi::fused, "8-bit float segments: NN, without operators");
     if (g.tile == 32) tile_fp8<32, true, CLS == 4, Chain>(g, ch, c, tm * 32, tn * 32, lane);
@@ -135,6 +144,7 @@ XAMD_SEG_KERNEL(gemm_segments_bf16_kernel, 1)
 XAMD_SEG_KERNEL(gemm_segments_f64_kernel, 2)
 XAMD_SEG_KERNEL(gemm_segments_bf8_kernel, 3)
 XAMD_SEG_KERNEL(gemm_segments_hf8_kernel, 4)
+XAMD_SEG_KERNEL(gemm_segments_f16_kernel, 5)
 #undef XAMD_SEG_KERNEL
 
 #define XAMD_SEG_FUSED_KERNEL(NAME, CLS) \
@@ -143,6 +153,7 @@ XAMD_SEG_KERNEL(gemm_segments_hf8_kernel, 4)
     segments_items<CLS, false, false>(g, seg_ptr, ListSource{a_list, b_list, c_list}, ListSegEpilogue{e}, total); }
 XAMD_SEG_FUSED_KERNEL(gemm_segments_f32_fused_kernel, 0)
 XAMD_SEG_FUSED_KERNEL(gemm_segments_bf16_fused_kernel, 1)
+XAMD_SEG_FUSED_KERNEL(gemm_segments_f16_fused_kernel, 5)
 #undef XAMD_SEG_FUSED_KERNEL
 
 #define XAMD_OFFS_KERNEL(NAME, CLS) \
@@ -154,6 +165,7 @@ XAMD_OFFS_KERNEL(gemm_segments_offs_bf16_kernel, 1)
 XAMD_OFFS_KERNEL(gemm_segments_offs_f64_kernel, 2)
 XAMD_OFFS_KERNEL(gemm_segments_offs_bf8_kernel, 3)          // 8-bit floats: only the NN instance <0,0> exists
 XAMD_OFFS_KERNEL(gemm_segments_offs_hf8_kernel, 4)
+XAMD_OFFS_KERNEL(gemm_segments_offs_f16_kernel, 5)
 #undef XAMD_OFFS_KERNEL
 
 #define XAMD_OFFS_FUSED_KERNEL(NAME, CLS) \
@@ -162,6 +174,7 @@ XAMD_OFFS_KERNEL(gemm_segments_offs_hf8_kernel, 4)
     segments_items<CLS, TA, TB>(g, seg_ptr, OffsetSource<const int&>{a_offs, b_offs, c_offs, e.a_wide}, OffsetSegEpilogue{e}, total); }
 XAMD_OFFS_FUSED_KERNEL(gemm_segments_offs_f32_fused_kernel, 0)
 XAMD_OFFS_FUSED_KERNEL(gemm_segments_offs_bf16_fused_kernel, 1)
+XAMD_OFFS_FUSED_KERNEL(gemm_segments_offs_f16_fused_kernel, 5)
 #undef XAMD_OFFS_FUSED_KERNEL
 
 // ---- sliced segments (libxsmm_hip_gemm_batch_reduce_segments_sliced, ..._offsets_sliced): a chain cut into slices that separate waves walk ------------------
@@ -184,6 +197,7 @@ XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_bf16_kernel, 1)
 XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_f64_kernel, 2)
 XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_bf8_kernel, 3)
 XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_hf8_kernel, 4)
+XAMD_SEG_SLICED_KERNEL(gemm_segments_sliced_f16_kernel, 5)
 #undef XAMD_SEG_SLICED_KERNEL
 
 #define XAMD_OFFS_SLICED_KERNEL(NAME, CLS) \
@@ -196,6 +210,13 @@ XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_f64_kernel, 2)
 XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_bf8_kernel, 3)   // <0,0> only
 XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_hf8_kernel, 4)
 #undef XAMD_OFFS_SLICED_KERNEL
+// f16, written out: its NT instance came out at 132 registers (3 waves per SIMD) where the bf16 sibling has 128 (4); it is held to the sibling's occupancy
+// (NN: no request).  No scratch results (profiles/r06_kernel_resources.txt).
+template <bool TA, bool TB> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TB ? 4 : 1)))
+void gemm_segments_offs_sliced_f16_kernel(GemmGroupDesc g, int a_wide, const unsigned long long* __restrict__ seg_ptr,
+    const long long* __restrict__ a_offs, const long long* __restrict__ b_offs, unsigned long long total) {
+  segments_items<5, TA, TB>(g, seg_ptr, SlicedSource<OffsetSource<int>>{OffsetSource<int>{a_offs, b_offs, nullptr, a_wide}}, NoSegEpilogue{}, total);
+}
 
 // Pass 2: acc = C (beta = 1) or +0, then acc += P_j for the block's slices j in ASCENDING order -- one IEEE add each in the accumulator type (the kernels run
 // with denormals kept), no atomics, no arrival order -- then one store with C's ldc and type.  CLS: 0 f32 partials -> f32 C, 1 f32 partials -> bf16 C
@@ -207,17 +228,24 @@ XAMD_OFFS_SLICED_KERNEL(gemm_segments_offs_sliced_hf8_kernel, 4)
 // item heads of pass 1, and the waves grid-stride in the same way.  C is read only under beta = 1 and written for i < m, j < n only: with m a multiple of V and
 // columns and block V-element aligned (`wide_ld`, then the pointer) a lane's V elements are one load / store of C, else element by element.  A block without
 // slices: beta = 0 stores +0, beta = 1 is skipped.  No LDS, no scratch, vector stores only.
+// The f16 class follows the reference's F16 loop instead: acc = +0, acc += P_j in ascending order, THEN acc += f16(C) widened (beta = 1),
+// then one store -- CLS 5: f16 C (cvt_pk_f16, the unsliced kernels' conversion), CLS 6: f32 C, rounded to a half on the way in.  The start comes last in the
+// unsliced kernels too, so one slice per block is the unsliced call bit for bit for both betas.  beta = 0 with an f32 C has no start and runs instance <0>.  A
+// block without slices under beta = 1 is skipped like every class's: an f32 C is NOT rounded there.
 // an element of C as the accumulator it starts
 template <int CLS, typename X> __device__ __forceinline__ auto slice_c_widen(X x) {
   if constexpr (CLS == 1) return bf16_bits_to_f32(x);
   else if constexpr (CLS == 3) return bf8_to_f32(x);
   else if constexpr (CLS == 4) return hf8_to_f32(x);
+  else if constexpr (CLS == 5) return (float)__builtin_bit_cast(_Float16, x);
+  else if constexpr (CLS == 6) return (float)(_Float16)x;                        // the f16 class with an f32 C: the start value is rounded to a half on the way in
   else return x;
 }
 template <int CLS>
 __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSliceReduce q, unsigned long long total) {
   typedef typename std::conditional<CLS == 2, double, float>::type acc_t;
-  typedef typename std::conditional<CLS == 2, double, typename std::conditional<CLS == 1, unsigned short, typename std::conditional<CLS >= 3, unsigned char, float>::type>::type>::type c_t;
+  typedef typename std::conditional<CLS == 2, double, typename std::conditional<CLS == 1 || CLS == 5, unsigned short, typename std::conditional<CLS == 3 || CLS == 4, unsigned char, float>::type>::type>::type c_t;
+  constexpr bool H16 = CLS >= 5;                                                 // the f16 class: the start value is added BEHIND the partials
   constexpr int V = 16 / (int)sizeof(acc_t);
   typedef acc_t vec_t __attribute__((ext_vector_type(V)));
   typedef c_t cvec_t __attribute__((ext_vector_type(V)));
@@ -254,6 +282,12 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSli
         }
       }
     }
+    [[maybe_unused]] vec_t start;
+    if constexpr (H16) {                                                       // the sum runs from +0; C (as a half, widened) joins it last
+      start = acc;
+#pragma unroll
+      for (int v = 0; v < V; ++v) acc[v] = (acc_t)0;
+    }
     gcptr p = (gcptr)q.ws + (long long)s0 * q.pstride + (long long)el * (long long)sizeof(acc_t);
     unsigned long long s = s0;
     for (; s + 4 <= s1; s += 4) {
@@ -262,8 +296,20 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSli
       acc += x0; acc += x1; acc += x2; acc += x3;
     }
     for (; s < s1; ++s) { acc += *(GM const vec_t*)p; p += q.pstride; }
+    if constexpr (H16) { if (q.beta1) acc += start; }
     if (!live) continue;
-    if constexpr (CLS >= 3) {
+    if constexpr (CLS == 5) {
+      const unsigned int pk[2] = {cvt_pk_f16((float)acc[0], (float)acc[1]), cvt_pk_f16((float)acc[2], (float)acc[3])};
+      if (wide) { u32x2 w = {pk[0], pk[1]}; *(GM u32x2*)cw = w; }
+      else {
+        unsigned int i = i0, j = j0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          if (e0 + v < mn) ((GM unsigned short*)c)[(long long)j * q.ldc + i] = (unsigned short)((v & 1) ? (pk[v / 2] >> 16) : (pk[v / 2] & 0xffffu));
+          if (++i == (unsigned int)q.m) { i = 0; ++j; }
+        }
+      }
+    } else if constexpr (CLS == 3 || CLS == 4) {
       const unsigned int w = f32x2_to_fp8_ref((float)acc[0], (float)acc[1], CLS == 4) | (f32x2_to_fp8_ref((float)acc[2], (float)acc[3], CLS == 4) << 16);
       if (wide) *(GM unsigned int*)cw = w;
       else {
@@ -304,7 +350,8 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSli
 // acc = start value of the unsliced ext entries (bias, bias + C in one f32 add, C or +0: acc_start in gemm_group_tile.hpp), then acc += P_j in ascending slice
 // order as above, then the mask bit !(acc <= 0), then act_fixed<1> / act_fixed<3>, then the store of pass 2.  A block without slices is NOT skipped: it stores
 // the activation of its start value and the mask taken from it, for every beta -- what the unsliced ext entry stores for a segment of count 0.  CLS: 0 f32 C,
-// 1 bf16 C (the bias has C's type).  The bias and mask entries of block b are wave-uniform scalar loads like C's entry.  No LDS, no scratch, vector stores only.
+// 1 bf16 C (the bias has C's type); the f16 class: 5 f16 C, 6 f32 C -- the start value is rounded to a half and added BEHIND the partials (slice_start_take),
+// the order of the unsliced f16 kernels, so a block without slices is their segment of count 0 and one slice per block is their call.  The bias and mask entries of block b are wave-uniform scalar loads like C's entry.  No LDS, no scratch, vector stores only.
 // Who writes a mask byte.  A byte holds 8 rows of ONE column; every byte is written by exactly one lane with one store, and no byte is ever read-merge-written by
 // two lanes.  Two ways of handing out the work, chosen by a wave-uniform test of the kernel arguments:
 //   runs   (no bitmask, or m % 8 == 0)  the work items of the plain kernel: lane l owns 4 consecutive elements of the dense partial, 16-byte loads.  With a
@@ -317,13 +364,27 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_kernel(GemmSli
 //          A unit's elements are consecutive in the dense partial but not 16-byte aligned: element loads, four slices in flight as above.  The lane owns all bits
 //          of its byte: a whole-byte store when 8 rows are valid, read-merge-write of the column's last byte by that one lane -- no other lane or wave touches it.
 template <int CLS> __device__ __forceinline__ float slice_c_load(const GM void* p, long long i) {
-  if constexpr (CLS == 1) return bf16_bits_to_f32(((GM const unsigned short*)p)[i]); else return ((GM const float*)p)[i];
+  if constexpr (CLS == 1) return bf16_bits_to_f32(((GM const unsigned short*)p)[i]);
+  else if constexpr (CLS == 5) return (float)((GM const _Float16*)p)[i];
+  else return ((GM const float*)p)[i];
+}
+// an element of a vector load of C or the bias
+template <int CLS, typename X> __device__ __forceinline__ float slice_c_wide(X x) {
+  if constexpr (CLS == 1) return bf16_bits_to_f32(x);
+  else if constexpr (CLS == 5) return (float)__builtin_bit_cast(_Float16, x);
+  else return x;
+}
+// The f16 class (CLS 5: f16 C and bias, 6: f32 C and bias) takes the start value LAST: what the loads above the partials built -- C, the bias, bias + C in one
+// f32 add -- is rounded to a half, widened and set aside, the sum runs from +0, and slice_start_add joins the two in one f32 add (nothing without a start).
+template <int CLS> __device__ __forceinline__ float slice_start_take(float& acc) {
+  if constexpr (CLS >= 5) { const float s = (float)(_Float16)acc; acc = 0.0f; return s; }
+  else return 0.0f;
 }
 
 template <int CLS>
 __device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q, const GemmSliceEpilogue& e, gptr c, gcptr d, GM unsigned char* mask, gcptr ws0,
   unsigned long long ns, unsigned int run, unsigned int lane) {
-  typedef typename std::conditional<CLS == 1, unsigned short, float>::type c_t;
+  typedef typename std::conditional<CLS == 1 || CLS == 5, unsigned short, float>::type c_t;
   constexpr int V = 4;
   typedef c_t cvec_t __attribute__((ext_vector_type(V)));
   const unsigned int m = (unsigned int)q.m, mn = m * (unsigned int)q.n;
@@ -338,7 +399,7 @@ __device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q,
     if (wide) {
       const cvec_t x = *(GM const cvec_t*)cw;
 #pragma unroll
-      for (int v = 0; v < V; ++v) { if constexpr (CLS == 1) acc[v] = bf16_bits_to_f32(x[v]); else acc[v] = x[v]; }
+      for (int v = 0; v < V; ++v) acc[v] = slice_c_wide<CLS>(x[v]);
     } else {
       unsigned int i = i0, j = j0;
 #pragma unroll
@@ -353,7 +414,7 @@ __device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q,
     if ((m & 3u) == 0 && ((unsigned int)(size_t)d & (unsigned int)(V * sizeof(c_t) - 1)) == 0) {
       const cvec_t x = *(GM const cvec_t*)((GM const c_t*)d + i0);
 #pragma unroll
-      for (int v = 0; v < V; ++v) { if constexpr (CLS == 1) bv[v] = bf16_bits_to_f32(x[v]); else bv[v] = x[v]; }
+      for (int v = 0; v < V; ++v) bv[v] = slice_c_wide<CLS>(x[v]);
     } else {
       unsigned int i = i0;
 #pragma unroll
@@ -361,6 +422,11 @@ __device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q,
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) acc[v] = q.beta1 ? bv[v] + acc[v] : bv[v];
+  }
+  [[maybe_unused]] f32x4 start;
+  if constexpr (CLS >= 5) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) { float x = acc[v]; start[v] = slice_start_take<CLS>(x); acc[v] = x; }
   }
   gcptr p = ws0 + (long long)el * 4;
   unsigned long long s = 0;
@@ -370,7 +436,8 @@ __device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q,
     acc += x0; acc += x1; acc += x2; acc += x3;
   }
   for (; s < ns; ++s) { acc += *(GM const f32x4*)p; p += q.pstride; }
-  if (e.act == 2) {                                                              // m % 8 == 0: the lane pair's byte, all 8 rows valid (every lane is active here)
+  if constexpr (CLS >= 5) { if (q.beta1 || e.colbias) acc += start; }
+  if (e.act == 2) {                                                           // m % 8 == 0: the lane pair's byte, all 8 rows valid (every lane is active here)
     unsigned int nib = 0;
 #pragma unroll
     for (int v = 0; v < V; ++v) nib |= (acc[v] <= 0.0f ? 0u : 1u) << v;
@@ -385,7 +452,18 @@ __device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q,
     for (int v = 0; v < V; ++v) acc[v] = act_fixed<1>(acc[v]);
   }
   if (!live) return;
-  if constexpr (CLS == 1) {
+  if constexpr (CLS == 5) {
+    const unsigned int pk[2] = {cvt_pk_f16(acc[0], acc[1]), cvt_pk_f16(acc[2], acc[3])};
+    if (wide) { u32x2 w = {pk[0], pk[1]}; *(GM u32x2*)cw = w; }
+    else {
+      unsigned int i = i0, j = j0;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        if (e0 + v < mn) ((GM unsigned short*)c)[(long long)j * q.ldc + i] = (unsigned short)((v & 1) ? (pk[v / 2] >> 16) : (pk[v / 2] & 0xffffu));
+        if (++i == m) { i = 0; ++j; }
+      }
+    }
+  } else if constexpr (CLS == 1) {
     float x[V]; unsigned int pk[V / 2];
 #pragma unroll
     for (int v = 0; v < V; ++v) x[v] = acc[v];
@@ -413,7 +491,7 @@ __device__ __forceinline__ void slice_reduce_fused_run(const GemmSliceReduce& q,
 template <int CLS>
 __device__ __forceinline__ void slice_reduce_fused_bytes(const GemmSliceReduce& q, const GemmSliceEpilogue& e, gptr c, gcptr d, GM unsigned char* mask, gcptr ws0,
   unsigned long long ns, unsigned int run, unsigned int lane) {
-  typedef typename std::conditional<CLS == 1, unsigned short, float>::type c_t;
+  typedef typename std::conditional<CLS == 1 || CLS == 5, unsigned short, float>::type c_t;
   const unsigned int m = (unsigned int)q.m, mq = (m + 7u) >> 3, units = mq * (unsigned int)q.n;
   for (unsigned int u0 = run * 64u; u0 < units; u0 += q.runs * 64u) {
     const bool live = u0 + lane < units;
@@ -431,6 +509,11 @@ __device__ __forceinline__ void slice_reduce_fused_bytes(const GemmSliceReduce& 
     if (e.colbias) {
 #pragma unroll
       for (int v = 0; v < 8; ++v) if ((unsigned int)v < nv) { const float bv = slice_c_load<CLS>(d, i0 + v); acc[v] = q.beta1 ? bv + acc[v] : bv; }
+    }
+    [[maybe_unused]] float start[8];
+    if constexpr (CLS >= 5) {
+#pragma unroll
+      for (int v = 0; v < 8; ++v) start[v] = slice_start_take<CLS>(acc[v]);
     }
     gcptr p = ws0 + ((long long)j * m + i0) * 4;
     unsigned long long s = 0;
@@ -456,6 +539,12 @@ __device__ __forceinline__ void slice_reduce_fused_bytes(const GemmSliceReduce& 
 #pragma unroll
       for (int v = 0; v < 8; ++v) acc[v] += x[v];
     }
+    if constexpr (CLS >= 5) {
+      if (q.beta1 || e.colbias) {
+#pragma unroll
+        for (int v = 0; v < 8; ++v) acc[v] += start[v];
+      }
+    }
     unsigned int bits = 0;
 #pragma unroll
     for (int v = 0; v < 8; ++v) bits |= ((unsigned int)v < nv && !(acc[v] <= 0.0f) ? 1u : 0u) << v;
@@ -466,7 +555,11 @@ __device__ __forceinline__ void slice_reduce_fused_bytes(const GemmSliceReduce& 
     }
 #pragma unroll
     for (int v = 0; v < 8; ++v) acc[v] = act_fixed<1>(acc[v]);
-    if constexpr (CLS == 1) {
+    if constexpr (CLS == 5) {
+      const unsigned int pk[4] = {cvt_pk_f16(acc[0], acc[1]), cvt_pk_f16(acc[2], acc[3]), cvt_pk_f16(acc[4], acc[5]), cvt_pk_f16(acc[6], acc[7])};
+#pragma unroll
+      for (int v = 0; v < 8; ++v) if (live && (unsigned int)v < nv) ((GM unsigned short*)cc)[v] = (unsigned short)((v & 1) ? (pk[v / 2] >> 16) : (pk[v / 2] & 0xffffu));
+    } else if constexpr (CLS == 1) {
       unsigned int pk[4];
       bf16_pk_exact_n<4>(acc, pk);
 #pragma unroll
@@ -501,23 +594,30 @@ __global__ __launch_bounds__(256) void gemm_segments_slice_reduce_fused_kernel(G
 
 // the four instances of an offsets kernel, indexed by forms & 3 (bit 0 TRANS_A, bit 1 TRANS_B)
 #define XAMD_FORMS(NAME) {NAME "<0,0>", NAME "<1,0>", NAME "<0,1>", NAME "<1,1>"}
-// rows: the classes 0 .. 4 (f32, bf16, f64, BF8, HF8), then (unsliced) the two fused classes; the 8-bit float offsets kernels have the NN instance only
-static const char* const kSlicedNames[5] = {"gemm_segments_sliced_f32_kernel", "gemm_segments_sliced_bf16_kernel", "gemm_segments_sliced_f64_kernel",
-  "gemm_segments_sliced_bf8_kernel", "gemm_segments_sliced_hf8_kernel"};
-static const char* const kOffsSlicedNames[5][4] = {XAMD_FORMS("gemm_segments_offs_sliced_f32_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf16_kernel"),
-  XAMD_FORMS("gemm_segments_offs_sliced_f64_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf8_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_hf8_kernel")};
-static const char* const kListNames[7] = {"gemm_segments_f32_kernel", "gemm_segments_bf16_kernel", "gemm_segments_f64_kernel", "gemm_segments_bf8_kernel",
-  "gemm_segments_hf8_kernel", "gemm_segments_f32_fused_kernel", "gemm_segments_bf16_fused_kernel"};
-static const char* const kOffsNames[7][4] = {XAMD_FORMS("gemm_segments_offs_f32_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_kernel"), XAMD_FORMS("gemm_segments_offs_f64_kernel"),
-  XAMD_FORMS("gemm_segments_offs_bf8_kernel"), XAMD_FORMS("gemm_segments_offs_hf8_kernel"), XAMD_FORMS("gemm_segments_offs_f32_fused_kernel"),
-  XAMD_FORMS("gemm_segments_offs_bf16_fused_kernel")};
+// f16: the NN and NT instances are all there is (launch_gemm_segments returns an error for the other two forms)
+#define XAMD_FORMS_NT(NAME) {NAME "<0,0>", nullptr, NAME "<0,1>", nullptr}
+// rows: the classes 0 .. 5 (f32, bf16, f64, BF8, HF8, f16), then (unsliced) the three fused classes f32, bf16, f16; the 8-bit float offsets kernels have the NN instance only
+static const char* const kSlicedNames[6] = {"gemm_segments_sliced_f32_kernel", "gemm_segments_sliced_bf16_kernel", "gemm_segments_sliced_f64_kernel",
+  "gemm_segments_sliced_bf8_kernel", "gemm_segments_sliced_hf8_kernel", "gemm_segments_sliced_f16_kernel"};
+static const char* const kOffsSlicedNames[6][4] = {XAMD_FORMS("gemm_segments_offs_sliced_f32_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf16_kernel"),
+  XAMD_FORMS("gemm_segments_offs_sliced_f64_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_bf8_kernel"), XAMD_FORMS("gemm_segments_offs_sliced_hf8_kernel"),
+  XAMD_FORMS_NT("gemm_segments_offs_sliced_f16_kernel")};
+static const char* const kListNames[9] = {"gemm_segments_f32_kernel", "gemm_segments_bf16_kernel", "gemm_segments_f64_kernel", "gemm_segments_bf8_kernel",
+  "gemm_segments_hf8_kernel", "gemm_segments_f16_kernel", "gemm_segments_f32_fused_kernel", "gemm_segments_bf16_fused_kernel", "gemm_segments_f16_fused_kernel"};
+static const char* const kOffsNames[9][4] = {XAMD_FORMS("gemm_segments_offs_f32_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_kernel"), XAMD_FORMS("gemm_segments_offs_f64_kernel"),
+  XAMD_FORMS("gemm_segments_offs_bf8_kernel"), XAMD_FORMS("gemm_segments_offs_hf8_kernel"), XAMD_FORMS_NT("gemm_segments_offs_f16_kernel"),
+  XAMD_FORMS("gemm_segments_offs_f32_fused_kernel"), XAMD_FORMS("gemm_segments_offs_bf16_fused_kernel"), XAMD_FORMS_NT("gemm_segments_offs_f16_fused_kernel")};
 #undef XAMD_FORMS
+#undef XAMD_FORMS_NT
 
 template <bool TA, bool TB>
 static void launch_offs_form(const SegmentsLaunch& l, unsigned int grid, hipStream_t st) {
   const long long* a_offs = (const long long*)l.a_list; const long long* b_offs = (const long long*)l.b_list; const long long* c_offs = (const long long*)l.c_list;
   if (l.fused) {
     const GemmSegOffsEpilogue& e = *(const GemmSegOffsEpilogue*)l.epilogue;
+    if constexpr (!TA) {                                   // f16: no handle has TRANS_A (dispatch refuses it: the reference's F16 loop has no transposed A), so NN and NT only
+      if (l.cls == 5) { hipLaunchKernelGGL((gemm_segments_offs_f16_fused_kernel<false, TB>), dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_offs, b_offs, c_offs, l.items); return; }
+    }
     if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_bf16_fused_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
     else hipLaunchKernelGGL((gemm_segments_offs_f32_fused_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
     return;
@@ -526,6 +626,9 @@ static void launch_offs_form(const SegmentsLaunch& l, unsigned int grid, hipStre
   if constexpr (!TA && !TB) {                              // 8-bit floats: the host refuses the transposed forms
     if (l.cls == 3) { hipLaunchKernelGGL((gemm_segments_offs_bf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items); return; }
     if (l.cls == 4) { hipLaunchKernelGGL((gemm_segments_offs_hf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items); return; }
+  }
+  if constexpr (!TA) {
+    if (l.cls == 5) { hipLaunchKernelGGL((gemm_segments_offs_f16_kernel<false, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items); return; }
   }
   if (l.cls == 2) hipLaunchKernelGGL((gemm_segments_offs_f64_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
   else if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_bf16_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, l.g, a_wide, l.seg_ptr, a_offs, b_offs, c_offs, l.items);
@@ -536,9 +639,11 @@ static void launch_list(const SegmentsLaunch& l, unsigned int grid, hipStream_t 
   const void* const* a_list = (const void* const*)l.a_list; const void* const* b_list = (const void* const*)l.b_list; void* const* c_list = (void* const*)l.c_list;
   if (l.fused) {
     const GemmSegEpilogue& e = *(const GemmSegEpilogue*)l.epilogue;
-    if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
+    if (l.cls == 5) hipLaunchKernelGGL(gemm_segments_f16_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
+    else if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
     else hipLaunchKernelGGL(gemm_segments_f32_fused_kernel, dim3(grid), dim3(256), 0, st, l.g, e, l.seg_ptr, a_list, b_list, c_list, l.items);
-  } else if (l.cls == 4) hipLaunchKernelGGL(gemm_segments_hf8_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+  } else if (l.cls == 5) hipLaunchKernelGGL(gemm_segments_f16_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
+  else if (l.cls == 4) hipLaunchKernelGGL(gemm_segments_hf8_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
   else if (l.cls == 3) hipLaunchKernelGGL(gemm_segments_bf8_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
   else if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_f64_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
   else if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_bf16_kernel, dim3(grid), dim3(256), 0, st, l.g, l.seg_ptr, a_list, b_list, c_list, l.items);
@@ -552,6 +657,9 @@ static void launch_offs_sliced_form(const SegmentsLaunch& l, const GemmGroupDesc
   if constexpr (!TA && !TB) {
     if (l.cls == 3) { hipLaunchKernelGGL((gemm_segments_offs_sliced_bf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items); return; }
     if (l.cls == 4) { hipLaunchKernelGGL((gemm_segments_offs_sliced_hf8_kernel<false, false>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items); return; }
+  }
+  if constexpr (!TA) {
+    if (l.cls == 5) { hipLaunchKernelGGL((gemm_segments_offs_sliced_f16_kernel<false, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items); return; }
   }
   if (l.cls == 2) hipLaunchKernelGGL((gemm_segments_offs_sliced_f64_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
   else if (l.cls == 1) hipLaunchKernelGGL((gemm_segments_offs_sliced_bf16_kernel<TA, TB>), dim3(grid), dim3(256), 0, st, g, a_wide, l.seg_ptr, a_offs, b_offs, l.items);
@@ -568,7 +676,8 @@ static int launch_sliced(const SegmentsLaunch& l, hipStream_t st, const char** k
     const unsigned int grid = group_grid(l.items);
     if (!l.offsets) {
       const void* const* a_list = (const void* const*)l.a_list; const void* const* b_list = (const void* const*)l.b_list;
-      if (l.cls == 4) hipLaunchKernelGGL(gemm_segments_sliced_hf8_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+      if (l.cls == 5) hipLaunchKernelGGL(gemm_segments_sliced_f16_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
+      else if (l.cls == 4) hipLaunchKernelGGL(gemm_segments_sliced_hf8_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
       else if (l.cls == 3) hipLaunchKernelGGL(gemm_segments_sliced_bf8_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
       else if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_sliced_f64_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
       else if (l.cls == 1) hipLaunchKernelGGL(gemm_segments_sliced_bf16_kernel, dim3(grid), dim3(256), 0, st, g, l.seg_ptr, a_list, b_list, l.items);
@@ -599,11 +708,16 @@ static int launch_sliced(const SegmentsLaunch& l, hipStream_t st, const char** k
       const GemmSegEpilogue& o = *(const GemmSegEpilogue*)l.epilogue;
       e.d_list = o.d_list; e.d = o.d; e.mask_list = o.mask_list; e.colbias = o.colbias; e.act = o.act; e.mask_ld = o.mask_ld;
     }
-    if (l.g.c_kind == 1) hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<1>, dim3(grid), dim3(256), 0, st, q, e, total);
+    if (l.cls == 5 && l.g.c_kind == 4) hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<5>, dim3(grid), dim3(256), 0, st, q, e, total);
+    else if (l.cls == 5) hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<6>, dim3(grid), dim3(256), 0, st, q, e, total);
+    else if (l.g.c_kind == 1) hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<1>, dim3(grid), dim3(256), 0, st, q, e, total);
     else hipLaunchKernelGGL(gemm_segments_slice_reduce_fused_kernel<0>, dim3(grid), dim3(256), 0, st, q, e, total);
     return (int)hipGetLastError();
   }
-  if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<2>, dim3(grid), dim3(256), 0, st, q, total);
+  // the f16 class adds its start value last (instances <5> f16 C, <6> f32 C under beta = 1); an f32 C under beta = 0 has none: instance <0>
+  if (l.cls == 5 && l.g.c_kind == 4) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<5>, dim3(grid), dim3(256), 0, st, q, total);
+  else if (l.cls == 5 && l.g.beta1) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<6>, dim3(grid), dim3(256), 0, st, q, total);
+  else if (l.cls == 2) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<2>, dim3(grid), dim3(256), 0, st, q, total);
   else if (l.g.c_kind == 1) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<1>, dim3(grid), dim3(256), 0, st, q, total);
   else if (l.g.c_kind == 2) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<3>, dim3(grid), dim3(256), 0, st, q, total);
   else if (l.g.c_kind == 3) hipLaunchKernelGGL(gemm_segments_slice_reduce_kernel<4>, dim3(grid), dim3(256), 0, st, q, total);
@@ -612,8 +726,10 @@ static int launch_sliced(const SegmentsLaunch& l, hipStream_t st, const char** k
 }
 
 int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname) {
+  // f16 kernels exist as NN and NT only (no handle has TRANS_A; segments_handle refuses one): an error here, never another class's kernel
+  if (l.cls == 5 && (l.forms & 1)) { *kname = ""; return (int)hipErrorInvalidValue; }
   if (l.sliced) return launch_sliced(l, (hipStream_t)stream, kname);
-  const int row = l.fused ? (l.cls == 1 ? 6 : 5) : l.cls;
+  const int row = l.fused ? (l.cls == 5 ? 8 : (l.cls == 1 ? 7 : 6)) : l.cls;
   *kname = l.offsets ? kOffsNames[row][l.forms & 3] : kListNames[row];
   if (l.items == 0) return 0;
   const unsigned int grid = group_grid(l.items);

@@ -118,7 +118,7 @@ struct GemmGroupDesc {
   unsigned long long br_count;                      // 1 for plain GEMM handles
   int m, n, k, lda, ldb, ldc;
   int tiles_m, tiles_n, tile;                       // C tiles of one element, tile edge 16 or 32
-  int beta1, vnni_a, c_kind;                        // beta = 1; A in VNNI layout (bf16: VNNI-2, 8-bit floats: VNNI-4); C's type: 0 f32 (f64 for class 2), 1 bf16, 2 BF8, 3 HF8
+  int beta1, vnni_a, c_kind;                        // beta = 1; A in VNNI layout (bf16 / f16: VNNI-2, 8-bit floats: VNNI-4); C's type: 0 f32 (f64 for class 2), 1 bf16, 2 BF8, 3 HF8, 4 f16
   int a_vec4;                                       // bf16 / 8-bit floats: VNNI A pairs / quads 4-byte aligned (every element, every block)
   int b_vec16, b_vec8;                              // B columns 16- / 8-byte aligned (every element, every block)
 };
@@ -319,11 +319,11 @@ inline unsigned int group_grid(unsigned long long items) { return (unsigned int)
 // device-accessible: pointers, or (offsets) signed byte offsets from the three bases in g.a / g.b / g.c.
 struct SegmentsLaunch {
   GemmGroupDesc g;
-  int cls, forms;                                   // cls: 0 f32, 1 bf16, 2 f64, 3 BF8, 4 HF8 (8-bit floats: NN only, never fused); forms (offsets): bit 0 TRANS_A, bit 1 TRANS_B, bit 2 / 3: lda spans a multiple of 16 / 8 bytes (the wide loads of a transposed A)
+  int cls, forms;                                   // cls: 0 f32, 1 bf16, 2 f64, 3 BF8, 4 HF8 (8-bit floats: NN only, never fused), 5 f16 (never TRANS_A: no such handle); forms (offsets): bit 0 TRANS_A, bit 1 TRANS_B, bit 2 / 3: lda spans a multiple of 16 / 8 bytes (the wide loads of a transposed A)
   unsigned long long items;                         // segments x C tiles
   const unsigned long long* seg_ptr;
   const void* a_list; const void* b_list; const void* c_list;
-  bool offsets, fused;                              // fused: the ext ABI's epilogue (column bias, ReLU (+ bitmask), sigmoid) in the store; cls 0 or 1
+  bool offsets, fused;                              // fused: the ext ABI's epilogue (column bias, ReLU (+ bitmask), sigmoid) in the store; cls 0, 1 or 5
   const void* epilogue;                             // fused: the GemmSegEpilogue, with offsets the GemmSegOffsEpilogue
   // the two *_sliced entries: `seg_ptr`, `a_list`, `b_list` and `items` are the SLICES' (items = slices x C tiles), `c_list` has one entry per block, and the
   // call is two launches: the slices' partials into `workspace`, `pstride` bytes apart, then the blocks' sums over blk_ptr (GemmSliceReduce)
@@ -351,7 +351,7 @@ struct GemmSliceEpilogue {
   int colbias, act, mask_ld;                        // as in GemmSegEpilogue
   int offs;
 };
-// bytes between the partials of a sliced call: m x n accumulators (f64 for class 2, else f32 -- the 8-bit float classes 3 and 4 among them), rounded up to 16
+// bytes between the partials of a sliced call: m x n accumulators (f64 for class 2, else f32 -- the 8-bit float classes 3 and 4 and the f16 class 5 among them), rounded up to 16
 inline unsigned long long slice_partial_stride(unsigned long long mn, int cls) { return (mn * (cls == 2 ? 8u : 4u) + 15u) & ~15ull; }
 inline unsigned int slice_reduce_runs(unsigned long long mn, int cls) { const unsigned int per = cls == 2 ? 128u : 256u; return (unsigned int)((mn + per - 1) / per); }
 int launch_gemm_segments(const SegmentsLaunch& l, void* stream, const char** kname);   // *kname: the kernel instance of class x forms x fused x offsets (sliced: of pass 1)

@@ -2283,8 +2283,10 @@ static GroupShape group_shape(const libxsmm_gemm_descriptor& d, unsigned int f, 
   // the 8-bit floats (segments only: grouped_eligible sends classes 3 and 4 on their own way): BF8 x BF8 -> f32 / BF8, HF8 x HF8 -> f32 / HF8
   const bool bf8 = d.a_type == LIBXSMM_DATATYPE_BF8 && d.b_type == LIBXSMM_DATATYPE_BF8 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_BF8);
   const bool hf8 = d.a_type == LIBXSMM_DATATYPE_HF8 && d.b_type == LIBXSMM_DATATYPE_HF8 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_HF8);
-  if (!f32 && !f64 && !bf16 && !bf8 && !hf8) return kGroupShapeTypes;
-  cls = f64 ? 2 : (bf16 ? 1 : (bf8 ? 3 : (hf8 ? 4 : 0)));
+  // IEEE halves (segments only, like the 8-bit floats): F16 x F16 -> f32 / F16
+  const bool f16 = d.a_type == LIBXSMM_DATATYPE_F16 && d.b_type == LIBXSMM_DATATYPE_F16 && (d.c_type == LIBXSMM_DATATYPE_F32 || d.c_type == LIBXSMM_DATATYPE_F16);
+  if (!f32 && !f64 && !bf16 && !bf8 && !hf8 && !f16) return kGroupShapeTypes;
+  cls = f64 ? 2 : (bf16 ? 1 : (bf8 ? 3 : (hf8 ? 4 : (f16 ? 5 : 0))));
   if (f & ~(kGroupTileFlags | own)) return kGroupShapeFlags;
   // element offsets inside one operand stay below 2^31 (the kernels index with 32-bit integers); a transposed operand spans lda x m / ldb x k
   const bool ta = (f & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (f & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
@@ -2295,8 +2297,8 @@ static GroupShape group_shape(const libxsmm_gemm_descriptor& d, unsigned int f, 
   g.m = (int)d.m; g.n = (int)d.n; g.k = (int)d.k; g.lda = (int)d.lda; g.ldb = (int)d.ldb; g.ldc = (int)d.ldc;
   g.tile = tile; g.tiles_m = (int)((d.m + tile - 1) / tile); g.tiles_n = (int)((d.n + tile - 1) / tile);
   g.beta1 = (f & LIBXSMM_GEMM_FLAG_BETA_0) ? 0 : 1;
-  g.vnni_a = ((bf16 || bf8 || hf8) && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
-  g.c_kind = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : (d.c_type == LIBXSMM_DATATYPE_BF8 ? 2 : (d.c_type == LIBXSMM_DATATYPE_HF8 ? 3 : 0));
+  g.vnni_a = ((bf16 || bf8 || hf8 || f16) && (f & LIBXSMM_GEMM_FLAG_VNNI_A)) ? 1 : 0;
+  g.c_kind = d.c_type == LIBXSMM_DATATYPE_BF16 ? 1 : (d.c_type == LIBXSMM_DATATYPE_BF8 ? 2 : (d.c_type == LIBXSMM_DATATYPE_HF8 ? 3 : (d.c_type == LIBXSMM_DATATYPE_F16 ? 4 : 0)));
   return kGroupShapeOk;
 }
 // ---- grouped batches (libxsmm_hip_gemm_batch_grouped, libxsmm_hip_gemm_ext_batch_grouped) and group plans (libxsmm_hip_gemm_group_plan_*) ------------------
@@ -2584,7 +2586,7 @@ LIBXSMM_API void libxsmm_hip_gemm_group_plan_destroy(libxsmm_hip_gemm_group_plan
 // What the four segments entries ask of their arguments and their handle, in one place: every refusal is set here, before anything is launched.  `ext` is the
 // entry (the two libxsmm_hip_gemm_ext_batch_reduce_segments* entries take ext handles and only those); `forms` != NULL is one of the two *_offsets entries, which
 // take OFFSET handles, three bases in param's primary slots (the lists are then a_offs / b_offs / c_offs) and transposed operands: *forms receives the bits
-// their kernels read.  (a, b and c sit at the same place in libxsmm_gemm_param and libxsmm_gemm_ext_param.)  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64, 3 BF8, 4 HF8) and `tiles` the C tiles of one segment.
+// their kernels read.  (a, b and c sit at the same place in libxsmm_gemm_param and libxsmm_gemm_ext_param.)  On success `g` holds the shape as the kernels read it, `cls` the kernel class (0 f32, 1 bf16, 2 f64, 3 BF8, 4 HF8, 5 f16) and `tiles` the C tiles of one segment.
 struct SegmentsSliced;
 static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, const void* param, size_t nsegments, GemmGroupDesc& g, int& cls, unsigned long long& tiles,
   int* forms, const SegmentsSliced* sl);
@@ -2639,11 +2641,16 @@ static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, 
     (ext ? (unsigned int)LIBXSMM_GEMM_FLAG_USE_XGEMM_EXT_ABI : 0u);
   const GroupShape shape = group_shape(d, f, own, g, cls);
   if (shape == kGroupShapeTypes) {
-    set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16, bf8 -> f32 / bf8, hf8 -> f32 / hf8)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return nullptr;
+    set_error(-3, "%s: operand types %s x %s -> %s are not taken (f32, f64, bf16 -> f32 / bf16, f16 -> f32 / f16, bf8 -> f32 / bf8, hf8 -> f32 / hf8)", fn, kTypeNames[d.a_type], kTypeNames[d.b_type], kTypeNames[d.c_type]); return nullptr;
+  }
+  if (cls == 5 && d.comp_type == LIBXSMM_DATATYPE_F16) {     // (GemmArgs::comp_f16: the dense generic kernel's arithmetic, not the matrix core's f32 chain)
+    set_error(-3, "%s: comp type F16 is not taken (the running sum is rounded to a half after every product, which only the dense generic kernel does)", fn); return nullptr;
   }
   const bool ta = (f & LIBXSMM_GEMM_FLAG_TRANS_A) != 0, tb = (f & LIBXSMM_GEMM_FLAG_TRANS_B) != 0;
   if (!offsets && (ta || tb)) { set_error(-3, "%s: transposed operands are not taken (NN only)", fn); return nullptr; }
-  if (cls >= 3 && shape != kGroupShapeTypes) {               // the 8-bit floats: the matrix-core layout of the dense kernels, NN
+  // (no f16 handle has TRANS_A -- gemm_supported refuses it, as the reference's F16 loop has no transposed A -- and the f16 offsets kernels exist as NN / NT only)
+  if (cls == 5 && ta) { set_error(-3, "%s: a transposed f16 A is not taken (F16 handles: NN and NT only)", fn); return nullptr; }
+  if ((cls == 3 || cls == 4) && shape != kGroupShapeTypes) {             // the 8-bit floats: the matrix-core layout of the dense kernels, NN
     if (ta || tb) { set_error(-3, "%s: transposed 8-bit float operands are not taken (BF8 / HF8 handles: NN only)", fn); return nullptr; }
     if (!(f & LIBXSMM_GEMM_FLAG_VNNI_A)) { set_error(-3, "%s: an 8-bit float A is taken as VNNI-4 only (LIBXSMM_GEMM_FLAG_VNNI_A)", fn); return nullptr; }
   }
@@ -2655,7 +2662,7 @@ static KernelCtx* segments_handle(const char* fn, bool ext, const void* kernel, 
   }
   if (shape == kGroupShapeLd) { set_error(-3, "%s: leading dimensions too large (element offsets inside an operand must stay below 2^31)", fn); return nullptr; }
   // what the leading dimension allows of the wider loads; the block pointers are tested per product on the device
-  const unsigned long long esz = cls == 1 ? 2 : (cls == 2 ? 8 : (cls >= 3 ? 1 : 4)), colb = (unsigned long long)d.ldb * esz;
+  const unsigned long long esz = (cls == 1 || cls == 5) ? 2 : (cls == 2 ? 8 : ((cls == 3 || cls == 4) ? 1 : 4)), colb = (unsigned long long)d.ldb * esz;
   g.a_vec4 = (cls == 1 || cls >= 3) ? 1 : 0; g.b_vec16 = (!tb && (colb & 15) == 0) ? 1 : 0; g.b_vec8 = (!tb && (colb & 7) == 0) ? 1 : 0;
   if (offsets) {
     const libxsmm_gemm_param* q = (const libxsmm_gemm_param*)param;
@@ -2680,7 +2687,7 @@ static bool segments_operators(const char* fn, const libxsmm_gemm_descriptor& d,
   }
   const bool colbias = colbias_out != 0;
   if (cls == 2 && (colbias || act != 0)) { set_error(-3, "%s: f64 ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
-  if (cls >= 3 && (colbias || act != 0)) { set_error(-3, "%s: 8-bit float ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
+  if ((cls == 3 || cls == 4) && (colbias || act != 0)) { set_error(-3, "%s: 8-bit float ext handles are taken without operators only (the fused epilogue is f32 / bf16)", fn); return false; }
   return true;
 }
 // The one path behind the four entries.  `offsets`: the lists hold signed byte offsets from the bases in param [ref: gemm ref :509-513, :186-188] -- a
